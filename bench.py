@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- vehicle-steps/sec of the HIP vehicle-step path (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over the whole ensemble: every vehicle
 advanced by dt = 1 ms, state read from and written back to HBM (no temporal
@@ -9,8 +9,9 @@ fusion in the headline number), one afe_step(e, dt, 1) call per step.  The
 engine runs in AFE_STEP_AUTO: up to 2^20 vehicles per GPU one resident grid
 serves the steps (afe_set_step_mode: no kernel boundary between two steps),
 beyond that one launch per step and half of the shard.  The timed region is
-repeated -- blocks of exactly K steps, each bracketed by barrier + synchronise --
-until 50 ms have been timed; the line carries the median block.  Workload: the
+exactly K steps in one block bracketed by barrier + synchronise, after W warm-up
+steps and a settle whose length follows from the arguments alone (settle_steps);
+ms_per_step is that block's time / K.  Workload: the
 config-4 shape of BASELINE.json -- a hovering MINIQUAD ensemble with a
 per-vehicle wind-gust force from the on-device gust process (the
 SetExternalForce port), IMU synthesis at the 500 Hz onboard-logic cadence with
@@ -31,15 +32,25 @@ neighbour / UWB-ranging consumers, at 100 Hz of simulated time -- is timed
 separately in `shared_world`.
 
 Prints ONE JSON line on rank 0 (see the repo task contract), kept below 6 kB
-(compact_line; tests/test_bench_line.py holds the bound), including
+(compact_line; tests/test_bench_line.py holds the bound).  A plain run measures the headline and nothing else.
+
+--dump-outputs DIR  after the timed block, rank 0 writes what those steps computed -- what afe_get_state_f32 and
+                    afe_get_imu hand a caller after the last step -- as DIR/<name>.npy, float32 [components, vehicles]:
+                    every vehicle up to DUMP_VEHICLES, else a fixed seeded sample of that many (headline_outputs).  The
+                    inputs, the warm-up and the settle depend on the arguments alone, so two runs with the same arguments
+                    step the same vehicles through the same steps.
+--full              everything else, as before.  `value` and `ms_per_step` stay the ONE timed block of the plain run (no
+                    longer the median of repeated blocks); after it the same engine repeats the block -- min / max in the
+                    line, the median in the side file (ms_per_step_median_of_blocks, vsteps_per_s_median_of_blocks: what
+                    scaling_check and tools/expected_rates.py use, the protocol profiles/expected_rates.json was taken in) --
+                    then the line gains
   roofline     -- algorithmic bytes / measured kernel time vs 8 TB/s, WHERE the working set lives (the 2^20 headline: the
                   256 MiB Infinity Cache; `traffic` is fabric-side bytes there), and `hbm_streaming`: the same kernels at
                   2^23 vehicles, where nothing survives a step on-die -- the path's true HBM row
   cpu_baseline -- the CPU oracle (port of the reference's algorithm) timed on
                   one host core over a bounded sample (rank 0, N = 1 only)
-Everything else that is measured (size sweep, perception rows, disturbance
-bins, shared-world worlds, notes) goes to the side file bench_detail.json
-(and gpurun_out/bench_detail.json where that directory exists).
+                and the other rows below.  Everything else that is measured (size sweep, perception rows, disturbance
+                bins, shared-world worlds, notes) goes to the side file bench_detail.json next to this file (write_detail).
 """
 import argparse
 import importlib
@@ -142,6 +153,50 @@ def time_steps(e, steps, per_launch, sync, barrier):
     t1 = time.perf_counter()      # this rank's own finish; the caller takes the MAX over ranks (the closing barrier's own
     barrier()                     # latency is not part of anybody's K steps)
     return t1 - t0
+
+
+# The headline's settle: timed_blocks settles for 30 ms of wall time, but the headline's ensemble must go through the same
+# steps in every run (--dump-outputs), so its settle is a number of steps fixed by the arguments -- ~30 ms at the 2^20 shard's
+# ~5e10 vehicle-steps/s, at most SETTLE_MAX_STEPS for the small shards.
+SETTLE_VEHICLE_STEPS = 1.5e9
+SETTLE_MAX_STEPS = 20000
+
+
+def settle_steps(n):
+    return int(min(SETTLE_MAX_STEPS, -(-SETTLE_VEHICLE_STEPS // n)))
+
+
+def settle(e, n, block_steps, sync, barrier):
+    """untimed blocks of (at most) the timed block's length between the warm-up and the timed block, settle_steps(n) steps
+    in all (why: timed_blocks), then the engine's first resident grid is ended like there"""
+    left = settle_steps(n)
+    while left > 0:
+        k = min(block_steps, left)
+        time_steps(e, k, 1, sync, barrier)
+        left -= k
+    e.grid_time()
+
+
+DUMP_VEHICLES = 1 << 19       # 92 B each (pos, vel, att, ang_vel, motor_speed, gyro, acc in float32): 48 MiB
+DUMP_SEED = 20
+
+
+def headline_outputs(e, n):
+    """what a caller of the timed path receives after its last step: the state (afe_get_state_f32) and the IMU sample of the
+    last logic tick (afe_get_imu), float32 [components, vehicles] -- every vehicle up to DUMP_VEHICLES, else a sample of that
+    many drawn with DUMP_SEED (the same vehicles in every run)"""
+    out = e.get_state(dtype=np.float32)
+    out["gyro"], out["acc"] = e.get_imu()
+    if n > DUMP_VEHICLES:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_VEHICLES, replace=False))
+        out = {k: np.ascontiguousarray(a[:, pick]) for k, a in out.items()}
+    return out
+
+
+def write_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def timed_blocks(e, steps, per_launch, sync, barrier, reduce_max, min_total_s=0.05, min_blocks=5, max_blocks=2000, own=None, settle_s=0.03):
@@ -1067,7 +1122,8 @@ def compact_line(full):
     if roof.get("hbm_streaming"):
         r["hbm_streaming"] = _pick(roof["hbm_streaming"], ("vehicles", "us_per_step", "achieved", "frac", "frac_of_6290", "probe_GBs", "ratio_to_stream_probe", "pmc_over_algorithmic",
                                                            "pmc_from", "stepping", "error"))
-    line["roofline"] = r
+    if "roofline" in full:          # (a plain run has none: --full measures it)
+        line["roofline"] = r
     cb = full.get("cpu_baseline")
     if cb:
         c = _pick(cb, ("value", "unit", "cores", "kind"))
@@ -1138,7 +1194,8 @@ def compact_line(full):
     c1 = full.get("config1_host_in_loop")
     if c1:
         line["config1_host_in_loop"] = _pick(c1, ("us_per_step", "realtime_factor", "error"))
-    line["detail"] = full.get("detail", DETAIL_FILE)
+    if full.get("detail", DETAIL_FILE):          # (None: a plain run, no side file)
+        line["detail"] = full.get("detail", DETAIL_FILE)
     line = _r(line)
     for victim in ("config1_host_in_loop", "shared_world", "closed_loop_on_device", "companions", "counter_noise_policy",
                    "north_star_shard", "config4_as_stated", "perception", "config5", "config3"):
@@ -1166,15 +1223,59 @@ _REAL_STDOUT = os.dup(1)       # the line goes here whatever fd 1 points at when
 _PRINTED = __import__("threading").Lock()
 
 
-def print_line_once(out):
+def print_line_once(out, detail=True):
     """exactly one JSON line on the real stdout, whoever gets here first (main thread or the watchdog): the compact
-    line; the full record goes to the side file"""
+    line; the full record goes to the side file (detail=False: a plain run, no side file)"""
     if not _PRINTED.acquire(blocking=False):
         return False
     sys.stdout.flush()
-    out["detail"] = write_detail(out)
+    out["detail"] = write_detail(out) if detail else None
     os.write(_REAL_STDOUT, (json.dumps(compact_line(out)) + "\n").encode())
     return True
+
+
+def headline_record(args, world, n_local, n_global, value, t_block, persistent, split):
+    """the line's contract keys and the workload of the headline, the same in a plain and in a --full run"""
+    return {
+        "metric": "vehicle-steps/sec @dt=1ms",
+        "value": value,
+        "unit": "vehicle-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": t_block / args.steps * 1e3,
+        "higher_is_better": True,
+        "headline_note": "since round 5 on the reference's noise streams; rounds 1-4 quoted counter_noise_policy" if HEADLINE_EXACT_STREAMS else None,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload_short": "BASELINE config 4 per GPU: %d hovering CF_MINIQUAD vehicles, per-vehicle wind gusts (sigma 0..0.5 N, 100 ms epochs), IMU "
+                              "synthesis + noise at the 500 Hz logic gate, one afe_step call per 1 ms step, state through memory every step" % n_local,
+            "noise": ("AFE_SEED_DECORRELATED: the reference's per-vehicle libstdc++ streams, bit-exact"
+                      if HEADLINE_EXACT_STREAMS else
+                      "AFE_SEED_COUNTER (Philox4x32-10 + Box-Muller); the reference's libstdc++ streams: reference_noise_streams"),
+            "parallelism_short": "contiguous shards, %d rank(s), no data-path collective" % world,
+            "workload": "config 4: hovering CF_MINIQUAD ensemble, per-vehicle wind gusts from the on-device gust process (sigma swept 0..0.5 N over "
+                        "the global index, piecewise constant, resampled every 100 ms; afe_set_gust_process), IMU synthesis with Gaussian noise from " +
+                        ("the reference's own machinery (one std::minstd_rand0 + std::normal_distribution stream per vehicle, seed 1 + global index: AFE_SEED_DECORRELATED)"
+                         if HEADLINE_EXACT_STREAMS else "the counter-based generator (AFE_SEED_COUNTER: Philox4x32-10 + Box-Muller per vehicle and tick)") +
+                        " at the 500 Hz logic gate, "
+                        "one afe_step call per 1 ms step, state through HBM every step (no temporal fusion); " +
+                        ("stepping by one resident grid (afe_set_step_mode: every wave advances its vehicles through each authorised step, "
+                         "no kernel boundary between steps)" if persistent else
+                         "one kernel launch per step" + (" and per half of the shard: the two halves step on two streams (afe_set_split_stepping)" if split else "")),
+            "vehicles_per_gpu": n_local,
+            "vehicles_total": n_global,
+            "dt_us": DT_US,
+            "logic_period_s": LOGIC_PERIOD,
+            "steps_per_call": 1,
+            "stepping": "persistent" if persistent else ("split launches" if split else "launches"),
+            "timing": "one block of exactly %d steps bracketed by barrier + synchronise, after %d warm-up and %d settle steps (--full: the same block repeated, min / max in ms_per_step_min / _max)" % (args.steps, args.warmup, settle_steps(n_local)),
+            "parallelism": "ensemble sharded contiguously, %d rank(s), no data-path collective" % world,
+        },
+    }
 
 
 def main():
@@ -1183,6 +1284,12 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--vehicles", type=int, default=1 << 20, help="vehicles per GPU (weak scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (state + IMU, float32) as DIR/<name>.npy; with --gpus > 1 "
+                         "rank 0's shard only")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated blocks, roofline, strong row, other noise policy, sweeps, perception, "
+                         "shared world, CPU baseline (the --no-* and --headline-only options below trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-shared-world", action="store_true")
@@ -1265,19 +1372,36 @@ def main():
     e = build_shard(afa, n_local, rank * n_local, n_global, local_rank)
     e.set_step_mode(mode)
 
-    # ---- the headline measurement: W warmup steps, then blocks of exactly K timed steps (median block) ----
+    # ---- the headline measurement: W warm-up steps, the settle, then ONE block of exactly K timed steps ----
     time_steps(e, args.warmup, 1, sync, barrier)
-    own_blocks = []
-    e.grid_time()         # (ends a resident grid and clears its account: what follows is the timed region's own)
-    blocks = timed_blocks(e, args.steps, 1, sync, barrier, reduce_max, own=own_blocks)
-    # device time of the resident grid over exactly that region (settling blocks included): the begin / end timestamps of
+    settle(e, n_local, args.steps, sync, barrier)
+    t_own = time_steps(e, args.steps, 1, sync, barrier)
+    t_head = reduce_max(t_own)            # the slowest rank's time for the block
+    value = n_global * args.steps / t_head
+    persistent = uses_persistent(afa, mode, n_local)
+    split = (not persistent) and n_local >= (1 << 19)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, headline_outputs(e, n_local))
+    if not args.full:
+        e.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print_line_once(headline_record(args, world, n_local, n_global, value, t_head, persistent, split), detail=False)
+        return
+
+    # ---- --full: the same block repeated on the same engine (after a settle of its own), as many times as timed_blocks
+    # takes; ms_per_step_min / _max are over the headline's block and these ----
+    own_blocks = [t_own]
+    e.grid_time()         # (ends a resident grid and clears its account: what follows is the repeats' own)
+    blocks = [t_head] + timed_blocks(e, args.steps, 1, sync, barrier, reduce_max, own=own_blocks)
+    # device time of the resident grid over exactly the repeats: the begin / end timestamps of
     # its dispatch(es) on the engine's queue and the steps served -- what a rocprofv3 kernel trace of this command shows
     # for the same dispatch (tools/profile_summary_r04.py).  (0, 0) when the steps were launched kernels.
     grid_s, grid_steps = e.grid_time()
-    persistent = uses_persistent(afa, mode, n_local)
-    split = (not persistent) and n_local >= (1 << 19)
     elapsed = median(blocks)
-    value = n_global * args.steps / elapsed
+    value_blocks = n_global * args.steps / elapsed     # the repeats' median: what profiles/expected_rates.json was measured as
 
     # ---- config 4 as BASELINE.json states it: 2^20 vehicles in total, sharded over the ranks (strong scaling) ----
     strong = None
@@ -1372,49 +1496,14 @@ def main():
                      "us_164B": us164, "us_132B": us132,
                      "what": "afe_stream_probe: back-to-back launches of a pure streaming kernel in the step kernel's shape (one-wave workgroups, "
                              "24+17 / 20+13 planar dword streams in place), same ensemble size, this run"}
-        out = {
-            "metric": "vehicle-steps/sec @dt=1ms",
-            "value": value,
-            "unit": "vehicle-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+        out = headline_record(args, world, n_local, n_global, value, t_head, persistent, split)
+        out.update({
             "repeats": len(blocks),
             "ms_per_step_min": min(blocks) / args.steps * 1e3,
             "ms_per_step_max": max(blocks) / args.steps * 1e3,
+            "ms_per_step_median_of_blocks": elapsed / args.steps * 1e3,
+            "vsteps_per_s_median_of_blocks": value_blocks,
             "ms_per_step_rank0_own": median(own_blocks) / args.steps * 1e3,     # `ms_per_step` is the MAX over ranks, block by block
-            "higher_is_better": True,
-            "headline_note": "since round 5 on the reference's noise streams; rounds 1-4 quoted counter_noise_policy" if HEADLINE_EXACT_STREAMS else None,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload_short": "BASELINE config 4 per GPU: %d hovering CF_MINIQUAD vehicles, per-vehicle wind gusts (sigma 0..0.5 N, 100 ms epochs), IMU "
-                                  "synthesis + noise at the 500 Hz logic gate, one afe_step call per 1 ms step, state through memory every step" % n_local,
-                "noise": ("AFE_SEED_DECORRELATED: the reference's per-vehicle libstdc++ streams, bit-exact"
-                          if HEADLINE_EXACT_STREAMS else
-                          "AFE_SEED_COUNTER (Philox4x32-10 + Box-Muller); the reference's libstdc++ streams: reference_noise_streams"),
-                "parallelism_short": "contiguous shards, %d rank(s), no data-path collective" % world,
-                "workload": "config 4: hovering CF_MINIQUAD ensemble, per-vehicle wind gusts from the on-device gust process (sigma swept 0..0.5 N over "
-                            "the global index, piecewise constant, resampled every 100 ms; afe_set_gust_process), IMU synthesis with Gaussian noise from " +
-                            ("the reference's own machinery (one std::minstd_rand0 + std::normal_distribution stream per vehicle, seed 1 + global index: AFE_SEED_DECORRELATED)"
-                             if HEADLINE_EXACT_STREAMS else "the counter-based generator (AFE_SEED_COUNTER: Philox4x32-10 + Box-Muller per vehicle and tick)") +
-                            " at the 500 Hz logic gate, "
-                            "one afe_step call per 1 ms step, state through HBM every step (no temporal fusion); " +
-                            ("stepping by one resident grid (afe_set_step_mode: every wave advances its vehicles through each authorised step, "
-                             "no kernel boundary between steps)" if persistent else
-                             "one kernel launch per step" + (" and per half of the shard: the two halves step on two streams (afe_set_split_stepping)" if split else "")),
-                "vehicles_per_gpu": n_local,
-                "vehicles_total": n_global,
-                "dt_us": DT_US,
-                "logic_period_s": LOGIC_PERIOD,
-                "steps_per_call": 1,
-                "stepping": "persistent" if persistent else ("split launches" if split else "launches"),
-                "timing": "median of %d blocks of exactly %d steps, each bracketed by barrier + synchronise (min / max in ms_per_step_min / _max)" % (len(blocks), args.steps),
-                "parallelism": "ensemble sharded contiguously, %d rank(s), no data-path collective" % world,
-            },
             "roofline": {
                 "bound": "hbm",
                 # where the headline's working set lives between two steps: every distinct byte a step touches (state 52 B, commands
@@ -1466,10 +1555,10 @@ def main():
             },
             "config4_as_stated": strong,
             "counter_noise_policy" if HEADLINE_EXACT_STREAMS else "reference_noise_streams": other,
-        }
+        })
         if world > 1:
             exp, exp_src = committed_json("expected_rates.json", lambda d: d)
-            sc = scaling_check(exp, exp_src, world, n_local, value, n_strong, strong["value"] if strong else None)
+            sc = scaling_check(exp, exp_src, world, n_local, value_blocks, n_strong, strong["value"] if strong else None)
             if sc:
                 out["scaling_check"] = sc
         # rows whose bytes are served by the Infinity Cache: their ceiling is what a pure streaming kernel of the step kernel's

@@ -141,6 +141,23 @@ def test_side_file_holds_the_full_record(tmp_path, monkeypatch):
         assert json.load(open(d / name)) == full
 
 
+def test_plain_run_line_holds_the_headline_alone():
+    """a run without --full prints the headline's contract keys and its workload, nothing it did not measure, and no side file
+    is named; its settle is a number of steps the arguments fix"""
+    import argparse
+    n, k, t_block = 1 << 20, 20, 4.2e-4
+    rec = bench.headline_record(argparse.Namespace(steps=k, warmup=5), 1, n, n, n * k / t_block, t_block, True, False)
+    rec["detail"] = None
+    line = json.loads(json.dumps(bench.compact_line(rec)))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert key in line, key
+    assert line["metric"] == "vehicle-steps/sec @dt=1ms" and line["unit"] == "vehicle-steps/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["ms_per_step"] == pytest.approx(t_block / k * 1e3) and line["value"] == pytest.approx(n / (line["ms_per_step"] * 1e-3), rel=1e-5)
+    for key in ("roofline", "detail", "cpu_baseline", "config4_as_stated", "repeats"):
+        assert key not in line, key
+    assert bench.settle_steps(1 << 20) == 1431 and bench.settle_steps(1024) == bench.SETTLE_MAX_STEPS
+
+
 def test_bound_fields_say_what_a_rate_is_a_fraction_of():
     ns = {"valu_instructions_per_wave_step": 460.0, "valu_active_frac": 0.39, "simd_valu_busy_frac": 0.78, "counters_from": "profiles/x.json"}
     small = bench.bound_fields(4096, 144.0, 1.6e-6, ns)                      # one wave on 64 of 1 024 SIMDs

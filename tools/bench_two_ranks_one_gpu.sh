@@ -8,7 +8,7 @@ set -u
 cd "$(dirname "$0")/.."
 export AFE_BENCH_ONE_DEVICE=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 \
-  bench.py --gpus 2 --steps 20 --warmup 5 --vehicles 131072 --no-shared-world > /tmp/two_ranks.out 2> /tmp/two_ranks.err
+  bench.py --gpus 2 --steps 20 --warmup 5 --vehicles 131072 --no-shared-world --full > /tmp/two_ranks.out 2> /tmp/two_ranks.err
 rc=$?
 echo "exit code $rc; stdout lines: $(wc -l < /tmp/two_ranks.out)"
 python3 - <<'PY'

@@ -32,7 +32,7 @@ for part in $PARTS; do
       bash $ROOT/tools/render_pmc.sh r05 > $OUT/render_pmc_r05.txt 2>&1 ;;
     full)
       cd /tmp
-      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_full_r05 -- python3 $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 > $OUT/prof_full_r05.log 2>&1
+      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_full_r05 -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $OUT/prof_full_r05.log 2>&1
       cd $ROOT ;;
   esac
 done
