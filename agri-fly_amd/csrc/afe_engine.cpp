@@ -563,6 +563,15 @@ int gust_resample(afe_engine *e, uint64_t epoch) {
   e->gust_applied = epoch;
   return AFE_OK;
 }
+// A resident grid started now keeps the commands and the external force in LDS for its lifetime (afe_kernels.hip
+// persist_holds, AFE_PERSIST_HOLD): the fp32 one-step grid with a force stream.  Sound because nothing but the grid itself
+// writes those slabs while it lives -- every host setter ends it first (main_stream -> persist_park), a gust epoch is
+// written by the grid's own waves -- with two exceptions, which read them from memory as before: a host-visible arena
+// (the host writes the slabs in place beside a grid that stays, copy_in) and an exported device view (a writer the engine
+// does not know about).  DESIGN.md section 2 lists the writers.
+bool persist_holds_inputs(const afe_engine *e, const LaunchFlags &f) {
+  return e->precision == AFE_F32 && f.ext_force && !f.ext_torque && !f.logic && !f.resident && !e->view_exported && !e->host_arena;
+}
 bool persist_eligible(const afe_engine *e) {
   if (e->step_mode == AFE_STEP_LAUNCH || e->p_failed) return false;
   if (e->step_mode == AFE_STEP_AUTO && e->n > (int64_t(1) << 20)) return false;   // measured: DESIGN.md section 6 (beyond the Infinity Cache the split launches are ahead)
@@ -721,7 +730,8 @@ int persist_launch(afe_engine *e) {
   const int64_t chunks_now = (e->n + 63) / 64;
   const bool prio = prio_env >= 0 ? prio_env != 0 : (e->p_workers > 4 * e->p_cus && chunks_now <= 2 * (int64_t)e->p_workers);
   e->p_prio = prio;
-  a.epoch = (++e->p_epoch & 0xffffu) | (e->host_arena ? AFE_PERSIST_HOST_IO : 0u) | (prio ? AFE_PERSIST_PRIO : 0u);
+  a.epoch = (++e->p_epoch & 0xffffu) | (e->host_arena ? AFE_PERSIST_HOST_IO : 0u) | (prio ? AFE_PERSIST_PRIO : 0u) |
+            (persist_holds_inputs(e, e->p_flags) ? AFE_PERSIST_HOLD : 0u);
   // The books at step p_resume, where this grid starts (the host's own clock, tick count and gust epoch are already
   // those of step p_next, the end of everything authorised): its start time is linear in the step index since
   // p_seg_start; the ticks before it are the engine's count less the tick flags of the entries still ahead of it;
@@ -1750,6 +1760,15 @@ extern "C" int afe_algorithmic_bytes_per_step(const afe_engine *e, int imu_tick,
   if (!e->types_uniform) b += 1;  // type index (heterogeneous ensembles only)
   if (e->has_ext_force) b += 3 * es;
   if (e->has_ext_torque) b += 3 * es;
+  if (e->step_mode == AFE_STEP_PERSISTENT && persist_eligible(e) && persist_holds_inputs(e, persist_flags(e))) {
+    // the resident grid that steps this engine reads the commands and the force once per grid, not per step -- for the
+    // first AFE_PERSIST_HELD_SLOTS chunks of every worker (all of them up to ~1.1 M vehicles); sized like the last grid
+    // (before the first one: every chunk held)
+    const int64_t chunks = (e->n + 63) / 64;
+    const int64_t held_chunks = e->p_workers > 0 ? std::min<int64_t>(chunks, (int64_t)AFE_PERSIST_HELD_SLOTS * e->p_workers) : chunks;
+    const double held = e->n > 0 ? (double)std::min<int64_t>(e->n, held_chunks * 64) / (double)e->n : 0.0;
+    b -= held * (4 * 4 + 3 * es);
+  }
   if (imu_tick) {
     b += 6 * 4;                // gyro + accelerometer sample
     if (e->noise && e->seed_policy != AFE_SEED_COUNTER) b += 8;   // RNG word read + write (the counter policy keeps no word)

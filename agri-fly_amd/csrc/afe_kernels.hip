@@ -561,6 +561,11 @@ __device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t r, uint32_t voff, 
   else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, val), r, (int)voff, (int)soff, AUX);
 }
 
+// A resident-grid worker's copy of its chunks' held inputs (AFE_PERSIST_HOLD): [slot][cmd 0-3, force 4-6][lane]
+struct HeldInputs {
+  float v[AFE_PERSIST_HELD_SLOTS][7][64];
+};
+
 // CP -- cache policy of the slab accesses (afe_set_cache_policy; memory hints only, never a different bit):
 //   0  default everywhere: an ensemble whose whole working set lives in the 256 MiB Infinity Cache (up to ~2^20 fp32 vehicles);
 //   1  the streams nobody re-reads soon -- inputs (commands, wrench) and outputs (IMU samples) -- are nt, the state is
@@ -568,9 +573,13 @@ __device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t r, uint32_t voff, 
 //      the inputs and outputs stream past it (tools/hbm_probe.hip);
 //   2  everything nt: beyond that nothing survives a step anyway, and lines that do not wait in the caches for a re-read
 //      that never comes make the write-backs cheaper (+6 % at 2^23, +10 % with one contiguous range per XCD = policy 3).
-template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool SINGLE, bool BUF, bool EACH = false, int CP = 0>
+//
+// HELD (the resident grid's one-step fp32 instantiations with an external force, persist_holds): the commands and the force
+// of a chunk the worker holds (held_slot >= 0, wave-uniform) come from the worker's LDS copy (HeldInputs), not from memory.
+template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool SINGLE, bool BUF, bool EACH = false, int CP = 0, bool HELD = false>
 __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParams<R> &P, const DevLogic &G,
-                                            const int64_t i, const unsigned long long tick_mask, const int n_steps_arg, const uint64_t tick_ordinal0) {
+                                            const int64_t i, const unsigned long long tick_mask, const int n_steps_arg, const uint64_t tick_ordinal0,
+                                            const HeldInputs *held = nullptr, const int held_slot = -1) {
   // No implicit FMA contraction: every rounding is the one the source spells
   // out, so all instantiations (noise on/off, wrench on/off, table/uniform,
   // fused or single-step) produce bit-identical physics, and the operation
@@ -644,6 +653,18 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
   // The engine word goes first: loads return in order, so the Gaussian draws of
   // this launch's first logic tick (which need nothing else) run while the ~24
   // state loads behind it are still in flight.
+  float cmd_f[4];
+  R fex = 0, fey = 0, fez = 0, tex = 0, tey = 0, tez = 0;
+  const bool from_lds = HELD && held_slot >= 0;
+  if (from_lds) {
+    // (ahead of every load: read where nothing is in flight, the LDS values never wait behind the memory ones.  One dword per
+    // lane per component: conflict-free; 28 B per vehicle-step that no longer cross the fabric)
+    static_assert(!HELD || (sizeof(R) == 4 && FEXT && !TEXT && !LOGIC), "held inputs: fp32 commands + force only");
+    const uint32_t ln = (uint32_t)i & 63u;
+#pragma unroll
+    for (int m = 0; m < 4; m++) cmd_f[m] = held->v[held_slot][m][ln];
+    fex = held->v[held_slot][4][ln]; fey = held->v[held_slot][5][ln]; fez = held->v[held_slot][6][ln];
+  }
   uint32_t rng = 0;
   if (NOISE == 1 && tick_mask) rng = AFE_LD(uint32_t, rng, 0, off4);
   uint64_t tick_ordinal = tick_ordinal0;   // NOISE == 2: the logic-tick number addresses the sample (wave-uniform)
@@ -656,9 +677,11 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
     ms[0] = AFE_LD(R, motor, 0, off); ms[1] = AFE_LD(R, motor, 1, off);
     ms[2] = AFE_LD(R, motor, 2, off); ms[3] = AFE_LD(R, motor, 3, off);
   }
-  const float cmd_f[4] = {AFE_LD(float, cmd, 0, off4), AFE_LD(float, cmd, 1, off4), AFE_LD(float, cmd, 2, off4), AFE_LD(float, cmd, 3, off4)};
-  R fex = 0, fey = 0, fez = 0, tex = 0, tey = 0, tez = 0;
-  if (FEXT) { fex = AFE_LD(R, ext_force, 0, off); fey = AFE_LD(R, ext_force, 1, off); fez = AFE_LD(R, ext_force, 2, off); }
+  if (!from_lds) {
+#pragma unroll
+    for (int m = 0; m < 4; m++) cmd_f[m] = AFE_LD(float, cmd, m, off4);
+    if (FEXT) { fex = AFE_LD(R, ext_force, 0, off); fey = AFE_LD(R, ext_force, 1, off); fez = AFE_LD(R, ext_force, 2, off); }
+  }
   if (TEXT) { tex = AFE_LD(R, ext_torque, 0, off); tey = AFE_LD(R, ext_torque, 1, off); tez = AFE_LD(R, ext_torque, 2, off); }
   LogicRegs lg;
 #define AFE_LOAD_LOGIC_STATE()                                        \
@@ -1241,6 +1264,11 @@ template <typename R, bool LOGIC, bool RESIDENT>
 constexpr int persistent_min_waves() { return sizeof(R) != 4 ? 1 : (!RESIDENT ? 6 : (LOGIC ? 3 : 5)); }
 // (resident state + logic, constants from LDS: 136-140 registers on their own, three waves; left alone the noise-free
 // instantiations take 214 and two.  Held to four waves: the same within the noise at every size.)
+// The instantiations that keep the held inputs in LDS when the engine says nothing else writes them (AFE_PERSIST_HOLD): the
+// fp32 one-step grid with an external force -- the headline's.  3 chunks x 64 lanes x 28 B = 5 376 B of LDS per one-wave
+// workgroup, 24 of them per CU at six waves per SIMD (129 KB of 160).  Every other instantiation reads them as before.
+template <typename R, bool FEXT, bool LOGIC, bool RESIDENT>
+constexpr bool persist_holds() { return sizeof(R) == 4 && FEXT && !LOGIC && !RESIDENT; }
 template <typename R, bool FEXT, int NOISE, bool LOGIC, bool RESIDENT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(persistent_min_waves<R, LOGIC, RESIDENT>())))
 afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const DevLogic G_arg, const PersistArgs a) {
@@ -1275,6 +1303,24 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
   u64_t gust_in_slab = a.gust_epoch_applied, gust_epoch = a.gust_epoch0;
   u64_t gust_next_us = (a.gust_epoch0 + 1) * a.gust_period_us, t_us = a.t0_us;
   bool sync_answered = false;                        // this wave has answered the sync marker standing at its count
+  // Held inputs (AFE_PERSIST_HOLD): the commands change only through host setters, and every one of them ends the grid first
+  // (afe_engine.cpp main_stream -> persist_park); the force only at a gust epoch, where this wave writes it itself.  So the
+  // wave reads both ONCE, into LDS, for its first AFE_PERSIST_HELD_SLOTS chunks, and each step takes them from there (28 of
+  // the 132 / 164 B per vehicle-step).  The slab is still written at a new epoch: observable, and the next grid starts from it.
+  constexpr bool HOLDS = persist_holds<R, FEXT, LOGIC, RESIDENT>();
+  __shared__ HeldInputs held_lds[1];                 // (unreferenced, and not allocated, where !HOLDS)
+  const bool hold = HOLDS && (a.epoch & AFE_PERSIST_HOLD);
+  if (HOLDS && hold) {
+    for (int j = 0, c = w; j < AFE_PERSIST_HELD_SLOTS && c < a.n_chunks; j++, c += a.n_workers) {
+      const int64_t i = (int64_t)c * 64 + lane;
+      if (i < v.n) {
+#pragma unroll
+        for (int m = 0; m < 4; m++) held_lds[0].v[j][m][lane] = v.cmd[m * v.stride + i];
+#pragma unroll
+        for (int k = 0; k < 3; k++) held_lds[0].v[j][4 + k][lane] = (float)v.ext_force[k * v.stride + i];
+      }
+    }
+  }
   // fewer chunks than the most loaded worker by a quarter or more: time to spare in every step
   const bool spare = 4 * ((a.n_chunks - w + a.n_workers - 1) / a.n_workers) <= 3 * ((a.n_chunks + a.n_workers - 1) / a.n_workers);
   for (;;) {
@@ -1384,22 +1430,28 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
       if (a.gust_period_us) {
         while (t_us >= gust_next_us) { gust_epoch++; gust_next_us += a.gust_period_us; }
         if (gust_epoch != gust_in_slab) {
-          for (int c = w; c < a.n_chunks; c += a.n_workers) {
+          for (int j = 0, c = w; c < a.n_chunks; j++, c += a.n_workers) {
             const int64_t i = (int64_t)c * 64 + lane;
             if (i < v.n) {
               R f[3];
               gust_force<R>(a.gust_seed, (uint64_t)(v.first_global + i), a.gust_n_global, gust_epoch, a.gust_sigma_max, f);
               R *slab = const_cast<R *>(v.ext_force);
               slab[i] = f[0]; slab[v.stride + i] = f[1]; slab[2 * v.stride + i] = f[2];
+              if (HOLDS && hold && j < AFE_PERSIST_HELD_SLOTS) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) held_lds[0].v[j][4 + k][lane] = (float)f[k];
+              }
             }
           }
           gust_in_slab = gust_epoch;
         }
         t_us += a.dt_us;
       }
-      for (int c = w; c < a.n_chunks; c += a.n_workers) {
+      for (int j = 0, c = w; c < a.n_chunks; j++, c += a.n_workers) {
         const int64_t i = (int64_t)c * 64 + lane;
-        if (i < v.n) run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true>(v, P, G, i, tick, 1, tick_no);
+        if (i < v.n)
+          run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true, false, 0, HOLDS>(v, P, G, i, tick, 1, tick_no, HOLDS ? &held_lds[0] : nullptr,
+                                                                                 hold && j < AFE_PERSIST_HELD_SLOTS ? j : -1);
       }
       tick_no += tick;
     }
