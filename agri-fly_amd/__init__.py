@@ -23,6 +23,8 @@ from .engine import (  # noqa: F401
     AFE_STEP_RESIDENT,
     AfeError,
     Camera,
+    ClearanceMap,
+    ContactMonitor,
     Comm,
     DeviceBuffer,
     DeviceView,
@@ -40,6 +42,7 @@ from .engine import (  # noqa: F401
     VehicleParams,
     build_library,
     camera_default,
+    clearance_check_hierarchy,
     gather_exchange,
     camera_default_mount,
     library,

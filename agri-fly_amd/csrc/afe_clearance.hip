@@ -1,0 +1,861 @@
+// afe_clearance.hip -- nearest point of a static triangle mesh for every vehicle (or explicit point), and the
+// device-resident contact monitor built on it.  The C ABI is in include/agrifly_engine.h ("mesh clearance").
+//
+// THE DEFINITION (tests/clearance_checker.py restates it in numpy float64, operation for operation; kernel and checker
+// must give the same bits, so the ORDER of the operations below is part of the contract).  Everything is IEEE double with
+// contraction off; only + - * / and comparisons appear, each correctly rounded on gfx950 and in numpy.
+//
+//   dot(u, v) = u.x*v.x + u.y*v.y + u.z*v.z                       (left to right)
+//   per triangle, once, at creation:   a = (double)v0,  ab = (double)v1 - a,  ac = (double)v2 - a,
+//        n = (ab.y*ac.z - ab.z*ac.y,  ab.z*ac.x - ab.x*ac.z,  ab.x*ac.y - ab.y*ac.x)
+//        degenerate  <=>  NOT( dot(n, n) > 1e-24 * (dot(ab, ab) * dot(ac, ac)) )       (sine of the corner at a <= 1e-12:
+//        coincident vertices and collinear triangles; a float32 sliver is NOT degenerate)
+//   per point p:   ap = p - a,  bp = ap - ab,  cp = ap - ac,
+//        d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp)
+//   tail(s, t):   m = ab*s + ac*t  (per axis),  q = ap - m,  dist2 = dot(q, q),  closest = a + m
+//
+//   REGIONS (Ericson, Real-Time Collision Detection, 5.1.5), tried in this order, the first that accepts gives (s, t);
+//   a region whose parameter is a quotient accepts only with a denominator > 0 (the textbook form divides 0 by 0 when a == b):
+//     A    d1 <= 0 and d2 <= 0                                                          (0, 0)
+//     B    d3 >= 0 and d4 <= d3                                                         (1, 0)
+//     AB   vc = d1*d4 - d3*d2;  vc <= 0 and d1 >= 0 and d3 <= 0 and (d1 - d3) > 0       (d1 / (d1 - d3), 0)
+//     C    d6 >= 0 and d5 <= d6                                                         (0, 1)
+//     AC   vb = d5*d2 - d1*d6;  vb <= 0 and d2 >= 0 and d6 <= 0 and (d2 - d6) > 0       (0, d2 / (d2 - d6))
+//     BC   va = d3*d6 - d5*d4;  e43 = d4 - d3, e56 = d5 - d6;
+//          va <= 0 and e43 >= 0 and e56 >= 0 and (e43 + e56) > 0                        t = e43 / (e43 + e56), s = 1 - t
+//     IN   den = (va + vb) + vc;  den > 0                                               r = 1 / den, s = vb*r, t = vc*r
+//   dist2 = tail(s, t).
+//
+//   SEGMENT RULE, used instead when the triangle is degenerate, when no region accepted, or when the dist2 above is not
+//   < +inf (which makes the definition total: a finite dist2 >= 0 for every finite triangle and point whose squares do
+//   not overflow).  The triangle is measured as the nearest of its three sides, parameters clamped, a side of zero length
+//   being its end point:  clamp(w) = w < 0 ? 0 : (w > 1 ? 1 : w)
+//     AB   l = dot(ab, ab);                 s = l > 0 ? clamp(d1 / l) : 0,          t = 0
+//     AC   l = dot(ac, ac);                 s = 0,                                  t = l > 0 ? clamp(d2 / l) : 0
+//     BC   e = ac - ab,  l = dot(e, e);     w = l > 0 ? clamp(dot(e, bp) / l) : 0,  s = 1 - w,  t = w
+//   dist2 = the smallest tail(s, t) of the three; a later side replaces an earlier one only when strictly smaller; a NaN
+//   replaces nothing (start from +inf).
+//
+//   WINNER over the triangles: only dist2 < +inf and dist2 <= max_dist2 count (max_dist2 = max_dist*max_dist, formed once
+//   on the host in double); the smallest dist2 wins, among bitwise-equal dist2 the lowest index in the order given to
+//   afe_clearance_map_create.  A point with no such triangle: dist2 = +inf, index -1, closest = NaN.  A point with a
+//   non-finite coordinate: the same, without a walk.
+//
+// THE STRUCTURE.  Its own handle and its own tree (the camera's, afe_render.hip, is built for 64 coherent rays walking by
+// scalar loads: pair nodes in eight mirrored copies with ray-inflated boxes).  Here the points of neighbouring lanes are not
+// neighbours in space, so the walk is per lane: a plain binary tree in one copy, median splits on the longest axis of the
+// centroid bounds with the input index as the tie-break (balanced whatever the centroids do: depth <= 2 + log2(n / 4), far below
+// the 32-entry stack), leaves of 1..4 triangles, exact float32 boxes.  A node record is 64 B, 32 B per child = two dwordx4
+// loads: {lo.xyz, ref}, {hi.xyz, -}.  Triangles whose box covers more than a quarter of the scene's (a ground plane's two;
+// at most 16) stay out of the tree and are tested first, brute force, which also gives every low-flying point its pruning
+// distance before the walk.
+//
+// NO OUTPUT BIT DEPENDS ON THE BOXES.  The box lower bound lb (per axis max(lo - p, 0, p - hi) in double, squared and summed)
+// may only ever err towards visiting: a subtree or triangle is skipped only if  lb * (1 - 2^-40) > best + E, with
+// E = 2^-40 * S and S = the squared distance from p to the farthest corner of the scene's box.  The computed dist2 of a
+// triangle differs from the exact one by rounding that is ABSOLUTE in the scale of the operands (q = ap - m cancels near the
+// surface): at most about 40 roundings of 1.1e-16 on terms bounded by |ap|^2 + |ab|^2 + |ac|^2 <= 9 S, i.e. 4e-14 S, twenty
+// times below E = 9e-13 S.  So a skipped triangle's computed dist2 is strictly greater than `best` and could neither win nor
+// tie.  (A relative slack alone would not do: a point on an edge has best = 0 and a neighbour's box 1e-9 away.)
+//
+// The walk's stack lives in LDS as [level][lane] (32 x 256 x 4 B = 32 KB per block, conflict-free: a lane only ever touches
+// its own column); a runtime-indexed private array would go to scratch.  Not covered: swept tests between two updates (see the header).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "afe_render.h"   // afe::engine_device_view / afe::engine_stream_device
+
+namespace afe {
+void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);   // afe_engine.cpp: the engine's size, nothing touched
+}
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kStack = 32;
+constexpr int kLeafMax = 4;
+constexpr int kMaxBig = 16;
+constexpr uint32_t kLeafBit = 0x80000000u, kNone = 0xffffffffu, kFirstMask = 0x0fffffffu;
+constexpr int64_t kMaxTri = 0x0ffffff0;
+constexpr int64_t kMaxPoints = int64_t(1) << 40;
+constexpr int64_t kPointsPerLaunch = int64_t(1) << 30;   // a launch stays below 2^31 threads (HIP truncates silently)
+
+// One triangle as the kernel wants it (112 B = seven dwordx4): box and identity first (one 32-byte fetch decides whether the
+// double-precision part is needed), then a, ab, ac already in double.
+struct CTri {
+  float lo[3], hi[3];
+  int32_t index;        // in the order given to afe_clearance_map_create
+  int32_t degenerate;   // the definition's flag
+  double a[3], ab[3], ac[3];
+  int32_t pad[2];
+};
+static_assert(sizeof(CTri) == 112, "seven dwordx4 per triangle");
+
+struct CChild {
+  float lo[3];
+  uint32_t ref;    // inner child: index of its CNode; leaf child: kLeafBit | count << 28 | first triangle (leaf order)
+  float hi[3];
+  uint32_t pad;
+};
+struct CNode { CChild c[2]; };
+static_assert(sizeof(CNode) == 64, "two dwordx4 per child");
+
+struct ClrArgs {
+  const CNode *nodes;
+  const CTri *tris;
+  uint32_t root_ref;          // kNone: nothing in the tree
+  uint32_t big_first, n_big;  // triangles kept out of the tree: slots [big_first, big_first + n_big)
+  float root_lo[3], root_hi[3];
+  double scene_lo[3], scene_hi[3];
+  double max_dist2;
+  // the points: planar, `stride` elements between components, element `first + i`
+  const void *pos;
+  const double *anchor_xy;    // engine state: x, y relative to this (afe_device_view::pos_anchor_xy); NULL: absolute
+  int64_t stride, first, count;
+  int elem_size;              // 4 or 8
+  // query outputs (any may be NULL), indexed by i; closest planar [3][out_stride]
+  double *dist2_out;
+  int32_t *tri_out;
+  double *closest_out;
+  int64_t out_stride;
+  // monitor latches, indexed by first + i
+  double *min_dist2;
+  uint64_t *first_us;
+  int32_t *first_tri;
+  unsigned long long *counts;   // [0] in contact now, [1] ever in contact
+  double contact2;
+  uint64_t now_us;
+  unsigned long long *stats;    // counting build: [0] nodes visited, [1] triangle box tests, [2] fp64 evaluations
+};
+
+struct Best {
+  double d2;
+  int32_t idx;
+  double cx, cy, cz;
+};
+
+__device__ __forceinline__ double clr_dot(double ax, double ay, double az, double bx, double by, double bz) {
+#pragma clang fp contract(off)
+  return ax * bx + ay * by + az * bz;
+}
+
+__device__ __forceinline__ double clr_clamp(double w) { return w < 0.0 ? 0.0 : (w > 1.0 ? 1.0 : w); }
+
+// squared distance from p to the box, in double from the exact float32 faces (lower bound of every distance into it)
+__device__ __forceinline__ double clr_box_lb(const float4 lo, const float4 hi, double px, double py, double pz) {
+#pragma clang fp contract(off)
+  const double dx = fmax(fmax((double)lo.x - px, 0.0), px - (double)hi.x);
+  const double dy = fmax(fmax((double)lo.y - py, 0.0), py - (double)hi.y);
+  const double dz = fmax(fmax((double)lo.z - pz, 0.0), pz - (double)hi.z);
+  return dx * dx + dy * dy + dz * dz;
+}
+
+// "may only err towards visiting": false for NaN, for best = +inf, for slack = +inf
+__device__ __forceinline__ bool clr_skip(double lb, double best, double slack) {
+#pragma clang fp contract(off)
+  return lb * (1.0 - 0x1p-40) > best + slack;
+}
+
+// the definition (file header), one triangle against one point; updates the winner
+__device__ __forceinline__ void clr_eval(const CTri *T, int32_t index, int32_t degenerate, double px, double py, double pz, Best &b) {
+#pragma clang fp contract(off)
+  const double ax = T->a[0], ay = T->a[1], az = T->a[2];
+  const double abx = T->ab[0], aby = T->ab[1], abz = T->ab[2];
+  const double acx = T->ac[0], acy = T->ac[1], acz = T->ac[2];
+  const double apx = px - ax, apy = py - ay, apz = pz - az;
+  const double bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
+  const double d1 = clr_dot(abx, aby, abz, apx, apy, apz), d2 = clr_dot(acx, acy, acz, apx, apy, apz);
+  double s = 0.0, t = 0.0, mx, my, mz, qx, qy, qz;
+  double d = std::numeric_limits<double>::infinity();
+  bool accepted = false;
+  if (!degenerate) {
+    const double cpx = apx - acx, cpy = apy - acy, cpz = apz - acz;
+    const double d3 = clr_dot(abx, aby, abz, bpx, bpy, bpz), d4 = clr_dot(acx, acy, acz, bpx, bpy, bpz);
+    const double d5 = clr_dot(abx, aby, abz, cpx, cpy, cpz), d6 = clr_dot(acx, acy, acz, cpx, cpy, cpz);
+    if (d1 <= 0.0 && d2 <= 0.0) { accepted = true; }
+    else if (d3 >= 0.0 && d4 <= d3) { s = 1.0; accepted = true; }
+    else {
+      const double vc = d1 * d4 - d3 * d2, den_ab = d1 - d3;
+      if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0 && den_ab > 0.0) { s = d1 / den_ab; accepted = true; }
+      else if (d6 >= 0.0 && d5 <= d6) { t = 1.0; accepted = true; }
+      else {
+        const double vb = d5 * d2 - d1 * d6, den_ac = d2 - d6;
+        if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0 && den_ac > 0.0) { t = d2 / den_ac; accepted = true; }
+        else {
+          const double va = d3 * d6 - d5 * d4, e43 = d4 - d3, e56 = d5 - d6, den_bc = e43 + e56;
+          if (va <= 0.0 && e43 >= 0.0 && e56 >= 0.0 && den_bc > 0.0) { t = e43 / den_bc; s = 1.0 - t; accepted = true; }
+          else {
+            const double den = (va + vb) + vc;
+            if (den > 0.0) { const double r = 1.0 / den; s = vb * r; t = vc * r; accepted = true; }
+          }
+        }
+      }
+    }
+    if (accepted) {
+      mx = abx * s + acx * t; my = aby * s + acy * t; mz = abz * s + acz * t;
+      qx = apx - mx; qy = apy - my; qz = apz - mz;
+      d = clr_dot(qx, qy, qz, qx, qy, qz);
+    }
+  }
+  if (!(d < std::numeric_limits<double>::infinity())) {     // the segment rule (degenerate / nothing accepted / not finite)
+    d = std::numeric_limits<double>::infinity();
+    s = 0.0; t = 0.0;
+    const double ex = acx - abx, ey = acy - aby, ez = acz - abz;
+    const double l_ab = clr_dot(abx, aby, abz, abx, aby, abz), l_ac = clr_dot(acx, acy, acz, acx, acy, acz);
+    const double l_bc = clr_dot(ex, ey, ez, ex, ey, ez);
+    const double w_ab = l_ab > 0.0 ? clr_clamp(d1 / l_ab) : 0.0;
+    const double w_ac = l_ac > 0.0 ? clr_clamp(d2 / l_ac) : 0.0;
+    const double w_bc = l_bc > 0.0 ? clr_clamp(clr_dot(ex, ey, ez, bpx, bpy, bpz) / l_bc) : 0.0;
+    for (int side = 0; side < 3; side++) {
+      const double ss = side == 0 ? w_ab : (side == 1 ? 0.0 : 1.0 - w_bc);
+      const double tt = side == 0 ? 0.0 : (side == 1 ? w_ac : w_bc);
+      const double nx = abx * ss + acx * tt, ny = aby * ss + acy * tt, nz = abz * ss + acz * tt;
+      const double rx = apx - nx, ry = apy - ny, rz = apz - nz;
+      const double dd = clr_dot(rx, ry, rz, rx, ry, rz);
+      if (dd < d) { d = dd; s = ss; t = tt; }
+    }
+    mx = abx * s + acx * t; my = aby * s + acy * t; mz = abz * s + acz * t;
+  }
+  if (d < std::numeric_limits<double>::infinity() && (d < b.d2 || (d == b.d2 && index < b.idx))) {
+    b.d2 = d;
+    b.idx = index;
+    b.cx = ax + mx; b.cy = ay + my; b.cz = az + mz;
+  }
+}
+
+// box of the triangle first (32 B), the double-precision part only if the box could hold a winner
+template <bool COUNT>
+__device__ __forceinline__ void clr_test(const CTri *T, double px, double py, double pz, double slack, Best &b, unsigned &n_box, unsigned &n_eval) {
+  const float4 *head = reinterpret_cast<const float4 *>(T);
+  const float4 h0 = head[0], h1 = head[1];        // lo.xyz hi.x | hi.yz index degenerate
+  float4 lo, hi;
+  lo.x = h0.x; lo.y = h0.y; lo.z = h0.z; lo.w = 0.0f;
+  hi.x = h0.w; hi.y = h1.x; hi.z = h1.y; hi.w = 0.0f;
+  if (COUNT) n_box++;
+  if (clr_skip(clr_box_lb(lo, hi, px, py, pz), b.d2, slack)) return;
+  if (COUNT) n_eval++;
+  clr_eval(T, __float_as_int(h1.z), __float_as_int(h1.w), px, py, pz, b);
+}
+
+template <bool MONITOR, bool COUNT>
+__global__ void __launch_bounds__(kBlock) afe_clearance_kernel(ClrArgs g) {
+#pragma clang fp contract(off)
+  __shared__ uint32_t stack[kStack][kBlock];
+  const int lane = threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + lane;
+  const bool valid = i < g.count;
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+  double px = nan, py = nan, pz = nan;
+  if (valid) {
+    const int64_t v = g.first + i;
+    if (g.elem_size == 8) {
+      const double *P = (const double *)g.pos;
+      px = P[v]; py = P[g.stride + v]; pz = P[2 * g.stride + v];
+    } else {
+      const float *P = (const float *)g.pos;
+      px = (double)P[v]; py = (double)P[g.stride + v]; pz = (double)P[2 * g.stride + v];
+    }
+    if (g.anchor_xy) { px = g.anchor_xy[v] + px; py = g.anchor_xy[g.stride + v] + py; }
+  }
+  Best b;
+  b.d2 = g.max_dist2; b.idx = 0x7fffffff; b.cx = nan; b.cy = nan; b.cz = nan;
+  unsigned n_nodes = 0, n_box = 0, n_eval = 0;
+  if (valid && __builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz)) {
+    // S: squared distance to the farthest corner of the scene's box (bounds |p - vertex|^2 for every vertex)
+    const double fx = fmax(fabs(px - g.scene_lo[0]), fabs(px - g.scene_hi[0]));
+    const double fy = fmax(fabs(py - g.scene_lo[1]), fabs(py - g.scene_hi[1]));
+    const double fz = fmax(fabs(pz - g.scene_lo[2]), fabs(pz - g.scene_hi[2]));
+    const double slack = 0x1p-40 * (fx * fx + fy * fy + fz * fz);
+    for (uint32_t k = 0; k < g.n_big; k++) clr_test<COUNT>(g.tris + g.big_first + k, px, py, pz, slack, b, n_box, n_eval);
+    uint32_t cur = g.root_ref;
+    if (cur != kNone) {
+      float4 lo, hi;
+      lo.x = g.root_lo[0]; lo.y = g.root_lo[1]; lo.z = g.root_lo[2]; lo.w = 0.0f;
+      hi.x = g.root_hi[0]; hi.y = g.root_hi[1]; hi.z = g.root_hi[2]; hi.w = 0.0f;
+      if (clr_skip(clr_box_lb(lo, hi, px, py, pz), b.d2, slack)) cur = kNone;
+    }
+    int sp = 0;
+    while (cur != kNone) {
+      if (cur & kLeafBit) {
+        const uint32_t first = cur & kFirstMask, cnt = (cur >> 28) & 7u;
+        for (uint32_t k = 0; k < cnt; k++) clr_test<COUNT>(g.tris + first + k, px, py, pz, slack, b, n_box, n_eval);
+        cur = kNone;
+      } else {
+        if (COUNT) n_nodes++;
+        const float4 *rec = reinterpret_cast<const float4 *>(g.nodes + cur);
+        const float4 lo0 = rec[0], hi0 = rec[1], lo1 = rec[2], hi1 = rec[3];
+        const double lb0 = clr_box_lb(lo0, hi0, px, py, pz), lb1 = clr_box_lb(lo1, hi1, px, py, pz);
+        const bool go0 = !clr_skip(lb0, b.d2, slack), go1 = !clr_skip(lb1, b.d2, slack);
+        const uint32_t ref0 = (uint32_t)__float_as_int(lo0.w), ref1 = (uint32_t)__float_as_int(lo1.w);
+        if (go0 && go1) {           // the nearer child now, the other one later
+          const bool near0 = lb0 <= lb1;
+          if (sp < kStack) stack[sp++][lane] = near0 ? ref1 : ref0;    // (the builder keeps the depth below kStack)
+          cur = near0 ? ref0 : ref1;
+          continue;
+        }
+        cur = go0 ? ref0 : (go1 ? ref1 : kNone);
+        if (cur != kNone) continue;
+      }
+      if (sp > 0) cur = stack[--sp][lane];
+    }
+  }
+  const bool found = b.idx != 0x7fffffff;
+  if (valid) {
+    if (g.dist2_out) g.dist2_out[i] = found ? b.d2 : inf;
+    if (g.tri_out) g.tri_out[i] = found ? b.idx : -1;
+    if (g.closest_out) {
+      g.closest_out[i] = found ? b.cx : nan;
+      g.closest_out[g.out_stride + i] = found ? b.cy : nan;
+      g.closest_out[2 * g.out_stride + i] = found ? b.cz : nan;
+    }
+  }
+  if (MONITOR) {
+    bool now = false, ever = false;
+    if (valid) {
+      const int64_t v = g.first + i;
+      if (found && b.d2 < g.min_dist2[v]) g.min_dist2[v] = b.d2;
+      now = found && b.d2 <= g.contact2;
+      uint64_t latched = g.first_us[v];
+      if (now && latched == ~uint64_t(0)) {
+        g.first_us[v] = g.now_us;
+        g.first_tri[v] = b.idx;
+        latched = g.now_us;
+      }
+      ever = latched != ~uint64_t(0);
+    }
+    // the two counts: ballot + popcount, then ONE vector atomic per wave (lanes 0 and 1 of it, one word each)
+    const unsigned long long n_now = (unsigned long long)__popcll(__ballot(now));
+    const unsigned long long n_ever = (unsigned long long)__popcll(__ballot(ever));
+    const int wl = lane & 63;
+    if (wl < 2 && (n_now | n_ever)) atomicAdd(g.counts + wl, wl == 0 ? n_now : n_ever);
+  }
+  if (COUNT && valid) {
+    atomicAdd(g.stats + 0, (unsigned long long)n_nodes);
+    atomicAdd(g.stats + 1, (unsigned long long)n_box);
+    atomicAdd(g.stats + 2, (unsigned long long)n_eval);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) afe_clearance_reset_kernel(double *min_dist2, uint64_t *first_us, int32_t *first_tri, int64_t first,
+                                                                      int64_t count) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= count) return;
+  min_dist2[first + i] = std::numeric_limits<double>::infinity();
+  first_us[first + i] = ~uint64_t(0);
+  first_tri[first + i] = -1;
+}
+
+// ---------------------------------------------------------------------------------------
+// host: the hierarchy
+// ---------------------------------------------------------------------------------------
+struct FBox {
+  float lo[3], hi[3];
+  void reset() { for (int k = 0; k < 3; k++) { lo[k] = std::numeric_limits<float>::infinity(); hi[k] = -lo[k]; } }
+  void grow(const float *p) { for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[k]); } }
+  void grow(const FBox &o) { grow(o.lo); grow(o.hi); }
+  double half_area() const {
+    const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
+    return x * y + y * z + z * x;
+  }
+  bool holds(const float *p) const { for (int k = 0; k < 3; k++) if (!(p[k] >= lo[k] && p[k] <= hi[k])) return false; return true; }
+  bool holds(const FBox &o) const { return holds(o.lo) && holds(o.hi); }
+};
+
+// the definition's flag, in the definition's operation order
+int degenerate_flag(const double ab[3], const double ac[3]) {
+#pragma clang fp contract(off)
+  const double n0 = ab[1] * ac[2] - ab[2] * ac[1], n1 = ab[2] * ac[0] - ab[0] * ac[2], n2 = ab[0] * ac[1] - ab[1] * ac[0];
+  const double nn = n0 * n0 + n1 * n1 + n2 * n2;
+  const double l_ab = ab[0] * ab[0] + ab[1] * ab[1] + ab[2] * ab[2], l_ac = ac[0] * ac[0] + ac[1] * ac[1] + ac[2] * ac[2];
+  return nn > 1e-24 * (l_ab * l_ac) ? 0 : 1;
+}
+
+struct HostMap {
+  const float *tri = nullptr;       // the caller's triangles
+  int64_t n_tri = 0, n_small = 0;
+  std::vector<int32_t> order;       // leaf order -> input index: the tree's triangles, then the ones kept out of it
+  std::vector<CNode> nodes;
+  uint32_t root_ref = kNone;
+  FBox root_box, scene;
+  int depth = 0, max_leaf = 0;
+
+  FBox tri_box(int32_t t) const {
+    FBox b; b.reset();
+    for (int v = 0; v < 3; v++) b.grow(tri + 9 * (int64_t)t + 3 * v);
+    return b;
+  }
+  double centroid(int32_t t, int axis) const {
+    const float *p = tri + 9 * (int64_t)t;
+    return ((double)p[axis] + (double)p[3 + axis]) + (double)p[6 + axis];
+  }
+  uint32_t build_range(int64_t lo, int64_t hi, int level, FBox &box) {
+    depth = std::max(depth, level);
+    box.reset();
+    for (int64_t k = lo; k < hi; k++) box.grow(tri_box(order[(size_t)k]));
+    if (hi - lo <= kLeafMax) {
+      max_leaf = std::max(max_leaf, (int)(hi - lo));
+      return kLeafBit | ((uint32_t)(hi - lo) << 28) | (uint32_t)lo;
+    }
+    double clo[3], chi[3];
+    for (int a = 0; a < 3; a++) { clo[a] = std::numeric_limits<double>::infinity(); chi[a] = -clo[a]; }
+    for (int64_t k = lo; k < hi; k++)
+      for (int a = 0; a < 3; a++) { const double c = centroid(order[(size_t)k], a); clo[a] = std::min(clo[a], c); chi[a] = std::max(chi[a], c); }
+    int axis = 0;
+    for (int a = 1; a < 3; a++) if (chi[a] - clo[a] > chi[axis] - clo[axis]) axis = a;
+    // median by count: balanced whatever the centroids are (all coincident: the split is by input index)
+    const int64_t mid = lo + (hi - lo) / 2;
+    std::nth_element(order.begin() + lo, order.begin() + mid, order.begin() + hi, [&](int32_t x, int32_t y) {
+      const double cx = centroid(x, axis), cy = centroid(y, axis);
+      return cx < cy || (cx == cy && x < y);
+    });
+    const size_t me = nodes.size();
+    nodes.push_back(CNode());
+    FBox b0, b1;
+    const uint32_t r0 = build_range(lo, mid, level + 1, b0);
+    const uint32_t r1 = build_range(mid, hi, level + 1, b1);
+    CNode &nd = nodes[me];
+    std::memset(&nd, 0, sizeof(nd));
+    for (int k = 0; k < 3; k++) { nd.c[0].lo[k] = b0.lo[k]; nd.c[0].hi[k] = b0.hi[k]; nd.c[1].lo[k] = b1.lo[k]; nd.c[1].hi[k] = b1.hi[k]; }
+    nd.c[0].ref = r0;
+    nd.c[1].ref = r1;
+    return (uint32_t)me;
+  }
+
+  int build(const float *triangles, int64_t n) {
+    tri = triangles; n_tri = n;
+    scene.reset();
+    for (int64_t i = 0; i < 3 * n; i++) scene.grow(triangles + 3 * i);
+    std::vector<int32_t> small_ix, big_ix;
+    const double scene_area = scene.half_area();
+    for (int64_t i = 0; i < n; i++) (tri_box((int32_t)i).half_area() > 0.25 * scene_area ? big_ix : small_ix).push_back((int32_t)i);
+    if ((int)big_ix.size() > kMaxBig || small_ix.empty()) {   // nothing special about this mesh: everything into the tree
+      small_ix.resize((size_t)n);
+      for (int64_t i = 0; i < n; i++) small_ix[(size_t)i] = (int32_t)i;
+      big_ix.clear();
+    }
+    n_small = (int64_t)small_ix.size();
+    order = small_ix;
+    nodes.clear(); depth = 0; max_leaf = 0;
+    root_ref = build_range(0, n_small, 1, root_box);
+    order.insert(order.end(), big_ix.begin(), big_ix.end());
+    return depth <= kStack ? AFE_OK : AFE_ERR_OUT_OF_RANGE;
+  }
+
+  // every triangle in exactly one leaf (or once in the out-of-tree list), every box holding what hangs below it
+  bool verify_ref(uint32_t ref, const FBox &box, int level, std::vector<int> &seen, int &deepest) const {
+    deepest = std::max(deepest, level);
+    if (level > kStack) return false;
+    if (ref & kLeafBit) {
+      const int64_t first = ref & kFirstMask, cnt = (ref >> 28) & 7u;
+      if (cnt < 1 || cnt > kLeafMax || first + cnt > n_small) return false;
+      for (int64_t k = first; k < first + cnt; k++) {
+        const int32_t t = order[(size_t)k];
+        seen[(size_t)t]++;
+        if (!box.holds(tri_box(t))) return false;
+      }
+      return true;
+    }
+    if (ref >= nodes.size()) return false;
+    const CNode &nd = nodes[ref];
+    for (int c = 0; c < 2; c++) {
+      FBox cb;
+      for (int k = 0; k < 3; k++) { cb.lo[k] = nd.c[c].lo[k]; cb.hi[k] = nd.c[c].hi[k]; }
+      if (!box.holds(cb) || !verify_ref(nd.c[c].ref, cb, level + 1, seen, deepest)) return false;
+    }
+    return true;
+  }
+  bool verify() const {
+    std::vector<int> seen((size_t)n_tri, 0);
+    int deepest = 0;
+    if (!scene.holds(root_box) || !verify_ref(root_ref, root_box, 1, seen, deepest) || deepest != depth) return false;
+    for (int64_t k = n_small; k < n_tri; k++) seen[(size_t)order[(size_t)k]]++;
+    for (int64_t t = 0; t < n_tri; t++) if (seen[(size_t)t] != 1) return false;
+    return true;
+  }
+
+  std::vector<CTri> pack() const {
+    std::vector<CTri> out((size_t)n_tri);
+    for (int64_t k = 0; k < n_tri; k++) {
+      const int32_t t = order[(size_t)k];
+      const float *src = tri + 9 * (int64_t)t;
+      CTri &T = out[(size_t)k];
+      std::memset(&T, 0, sizeof(T));
+      const FBox tb = tri_box(t);
+      for (int a = 0; a < 3; a++) {
+        T.lo[a] = tb.lo[a]; T.hi[a] = tb.hi[a];
+        T.a[a] = (double)src[a];
+        T.ab[a] = (double)src[3 + a] - T.a[a];
+        T.ac[a] = (double)src[6 + a] - T.a[a];
+      }
+      T.index = t;
+      T.degenerate = degenerate_flag(T.ab, T.ac);
+    }
+    return out;
+  }
+};
+
+bool mesh_ok(const float *triangles, int64_t n_tri) {
+  if (!triangles || n_tri <= 0 || n_tri > kMaxTri) return false;
+  for (int64_t i = 0; i < 9 * n_tri; i++) if (!std::isfinite(triangles[i])) return false;
+  return true;
+}
+
+int pick_gfx950(int device, int *out) {
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return AFE_ERR_NO_DEVICE;
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return AFE_ERR_NO_DEVICE;
+  if (device >= n_dev) return AFE_ERR_NO_DEVICE;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return AFE_ERR_NO_DEVICE;
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  *out = device;
+  return AFE_OK;
+}
+
+struct DevMem {
+  void *p = nullptr;
+  ~DevMem() { if (p) (void)hipFree(p); }
+  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+};
+
+}  // namespace
+
+struct afe_clearance_map {
+  int device = 0;
+  int64_t n_tri = 0, n_nodes = 0;
+  int depth = 0;
+  double bounds[6] = {0, 0, 0, 0, 0, 0};
+  CNode *nodes = nullptr;
+  CTri *tris = nullptr;
+  ClrArgs base;         // the tree's part of the kernel arguments
+};
+
+struct afe_contact_monitor {
+  afe_engine *engine = nullptr;        // borrowed
+  afe_clearance_map *map = nullptr;    // borrowed
+  int64_t n = 0;
+  int device = 0;
+  double contact2 = 0, search2 = 0;
+  double *min_dist2 = nullptr;
+  uint64_t *first_us = nullptr;
+  int32_t *first_tri = nullptr;
+  unsigned long long *counts = nullptr;       // device, two words
+  unsigned long long *counts_host = nullptr;  // pinned, two words
+};
+
+namespace {
+
+// launches the query for `count` points on `stream`, in runs below 2^31 threads
+template <bool MONITOR, bool COUNT>
+int launch_query(ClrArgs g, hipStream_t stream, float *kernel_ms) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) { if (e0) (void)hipEventDestroy(e0); return AFE_ERR_HIP; }
+  if (kernel_ms) (void)hipEventRecord(e0, stream);
+  int rc = AFE_OK;
+  const int64_t total = g.count, first = g.first;
+  double *d2 = g.dist2_out, *cl = g.closest_out;
+  int32_t *ti = g.tri_out;
+  for (int64_t done = 0; done < total && rc == AFE_OK; done += kPointsPerLaunch) {
+    const int64_t n = std::min(total - done, kPointsPerLaunch);
+    g.first = first + done;
+    g.count = n;
+    g.dist2_out = d2 ? d2 + done : nullptr;
+    g.tri_out = ti ? ti + done : nullptr;
+    g.closest_out = cl ? cl + done : nullptr;
+    hipLaunchKernelGGL((afe_clearance_kernel<MONITOR, COUNT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, g);
+    rc = hipGetLastError() == hipSuccess ? AFE_OK : AFE_ERR_HIP;
+  }
+  if (kernel_ms) {
+    (void)hipEventRecord(e1, stream);
+    if (rc == AFE_OK && hipEventSynchronize(e1) != hipSuccess) rc = AFE_ERR_HIP;
+    if (rc == AFE_OK) (void)hipEventElapsedTime(kernel_ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  }
+  return rc;
+}
+
+bool radius_ok(double max_dist) { return max_dist > 0.0; }   // false for NaN, 0, negatives; +inf passes
+
+int query_points(afe_clearance_map *m, int64_t n_points, const double *pos, double max_dist, double *dist2_out, int32_t *tri_out,
+                 double *closest_out, float *kernel_ms, uint64_t *stats) {
+  if (hipSetDevice(m->device) != hipSuccess) return AFE_ERR_HIP;
+  const size_t n = (size_t)n_points;
+  DevMem d_pos, d_d2, d_tri, d_cl, d_stats;
+  if (!d_pos.alloc(n * 24) || !d_d2.alloc(n * 8) || !d_tri.alloc(n * 4) || (closest_out && !d_cl.alloc(n * 24)) || (stats && !d_stats.alloc(24))) {
+    (void)hipGetLastError();
+    return AFE_ERR_HIP;
+  }
+  if (hipMemcpy(d_pos.p, pos, n * 24, hipMemcpyHostToDevice) != hipSuccess) return AFE_ERR_HIP;
+  if (stats && hipMemset(d_stats.p, 0, 24) != hipSuccess) return AFE_ERR_HIP;
+  ClrArgs g = m->base;
+  g.max_dist2 = max_dist * max_dist;
+  g.pos = d_pos.p; g.anchor_xy = nullptr; g.stride = n_points; g.first = 0; g.count = n_points; g.elem_size = 8;
+  g.dist2_out = (double *)d_d2.p; g.tri_out = (int32_t *)d_tri.p; g.closest_out = (double *)d_cl.p; g.out_stride = n_points;
+  g.stats = (unsigned long long *)d_stats.p;
+  float ms = 0;
+  const int rc = stats ? launch_query<false, true>(g, nullptr, &ms) : launch_query<false, false>(g, nullptr, &ms);
+  if (rc != AFE_OK) return rc;
+  if (kernel_ms) *kernel_ms = ms;
+  if (hipMemcpy(dist2_out, d_d2.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tri_out, d_tri.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      (closest_out && hipMemcpy(closest_out, d_cl.p, n * 24, hipMemcpyDeviceToHost) != hipSuccess))
+    return AFE_ERR_HIP;
+  if (stats) {
+    unsigned long long host[3];
+    if (hipMemcpy(host, d_stats.p, 24, hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
+    for (int k = 0; k < 3; k++) stats[k] = host[k];
+    stats[3] = (uint64_t)n_points;
+  }
+  return AFE_OK;
+}
+
+}  // namespace
+
+extern "C" int afe_clearance_map_create(int device, const float *triangles, int64_t n_tri, afe_clearance_map **out) {
+  if (!out || !mesh_ok(triangles, n_tri)) return AFE_ERR_INVALID_ARG;
+  int dev = 0;
+  int rc = pick_gfx950(device, &dev);
+  if (rc != AFE_OK) return rc;
+  HostMap h;
+  rc = h.build(triangles, n_tri);
+  if (rc != AFE_OK) return rc;
+  const std::vector<CTri> packed = h.pack();
+  afe_clearance_map *m = new afe_clearance_map();
+  m->device = dev;
+  m->n_tri = n_tri;
+  m->n_nodes = (int64_t)h.nodes.size();
+  m->depth = h.depth;
+  for (int k = 0; k < 3; k++) { m->bounds[k] = h.scene.lo[k]; m->bounds[3 + k] = h.scene.hi[k]; }
+  const size_t node_bytes = std::max<size_t>(h.nodes.size(), 1) * sizeof(CNode);
+  if (hipMalloc((void **)&m->nodes, node_bytes) != hipSuccess || hipMalloc((void **)&m->tris, packed.size() * sizeof(CTri)) != hipSuccess ||
+      (!h.nodes.empty() && hipMemcpy(m->nodes, h.nodes.data(), h.nodes.size() * sizeof(CNode), hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(m->tris, packed.data(), packed.size() * sizeof(CTri), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)afe_clearance_map_destroy(m);
+    return AFE_ERR_HIP;
+  }
+  ClrArgs &g = m->base;
+  std::memset(&g, 0, sizeof(g));
+  g.nodes = m->nodes; g.tris = m->tris;
+  g.root_ref = h.root_ref;
+  g.big_first = (uint32_t)h.n_small; g.n_big = (uint32_t)(n_tri - h.n_small);
+  for (int k = 0; k < 3; k++) {
+    g.root_lo[k] = h.root_box.lo[k]; g.root_hi[k] = h.root_box.hi[k];
+    g.scene_lo[k] = (double)h.scene.lo[k]; g.scene_hi[k] = (double)h.scene.hi[k];
+  }
+  *out = m;
+  return AFE_OK;
+}
+
+extern "C" int afe_clearance_map_destroy(afe_clearance_map *m) {
+  if (!m) return AFE_ERR_INVALID_ARG;
+  (void)hipSetDevice(m->device);
+  (void)hipDeviceSynchronize();      // a query on some stream may still be reading the tables
+  if (m->nodes) (void)hipFree(m->nodes);
+  if (m->tris) (void)hipFree(m->tris);
+  delete m;
+  return AFE_OK;
+}
+
+extern "C" int afe_clearance_map_info(const afe_clearance_map *m, int64_t *n_tri, int64_t *n_nodes, int *depth, double bounds[6]) {
+  if (!m) return AFE_ERR_INVALID_ARG;
+  if (n_tri) *n_tri = m->n_tri;
+  if (n_nodes) *n_nodes = m->n_nodes;
+  if (depth) *depth = m->depth;
+  if (bounds) for (int k = 0; k < 6; k++) bounds[k] = m->bounds[k];
+  return AFE_OK;
+}
+
+extern "C" int afe_clearance_check_hierarchy(const float *triangles, int64_t n_tri, int64_t *n_nodes, int *depth, int *max_leaf) {
+  if (!mesh_ok(triangles, n_tri)) return AFE_ERR_INVALID_ARG;
+  HostMap h;
+  const int rc = h.build(triangles, n_tri);
+  if (rc != AFE_OK) return rc;
+  if (!h.verify()) return AFE_ERR_OUT_OF_RANGE;
+  if (n_nodes) *n_nodes = (int64_t)h.nodes.size();
+  if (depth) *depth = h.depth;
+  if (max_leaf) *max_leaf = h.max_leaf;
+  return AFE_OK;
+}
+
+extern "C" int afe_clearance_query(afe_clearance_map *m, int64_t n_points, const double *pos, double max_dist, double *dist2_out,
+                                   int32_t *tri_out, double *closest_out, float *kernel_ms) {
+  if (!m || n_points < 0 || !pos || !dist2_out || !tri_out || !radius_ok(max_dist)) return AFE_ERR_INVALID_ARG;
+  if (n_points > kMaxPoints) return AFE_ERR_OUT_OF_RANGE;
+  if (n_points == 0) return AFE_OK;
+  return query_points(m, n_points, pos, max_dist, dist2_out, tri_out, closest_out, kernel_ms, nullptr);
+}
+
+extern "C" int afe_clearance_query_stats(afe_clearance_map *m, int64_t n_points, const double *pos, double max_dist, uint64_t stats[4],
+                                         float *kernel_ms) {
+  if (!m || n_points <= 0 || !pos || !stats || !radius_ok(max_dist)) return AFE_ERR_INVALID_ARG;
+  if (n_points > kMaxPoints) return AFE_ERR_OUT_OF_RANGE;
+  std::vector<double> d2((size_t)n_points);
+  std::vector<int32_t> ti((size_t)n_points);
+  return query_points(m, n_points, pos, max_dist, d2.data(), ti.data(), nullptr, kernel_ms, stats);
+}
+
+extern "C" int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t count, double max_dist, void *dist2_out,
+                                          void *tri_out, void *closest_out, int out_is_device, float *kernel_ms) {
+  if (!e || !m || first < 0 || count < 0 || !radius_ok(max_dist)) return AFE_ERR_INVALID_ARG;
+  if (count > 0 && (!dist2_out || !tri_out)) return AFE_ERR_INVALID_ARG;
+  {
+    int64_t first_global = 0, n = 0;
+    afe::engine_shard(e, &first_global, &n);
+    if (first > n || count > n - first) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
+    if (count == 0) return AFE_OK;          // a valid range of nothing: answered before the engine is touched
+  }
+  hipStream_t stream = nullptr;
+  int device = 0;
+  afe::engine_stream_device(e, (void **)&stream, &device);     // (ends a resident grid, as the camera does)
+  if (device != m->device) return AFE_ERR_INVALID_ARG;
+  afe_device_view view;
+  view.struct_bytes = sizeof(view);
+  int rc = afe::engine_device_view(e, &view);
+  if (rc != AFE_OK) return rc;
+  if (first > view.n_vehicles || count > view.n_vehicles - first) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  const size_t n = (size_t)count;
+  DevMem d_d2, d_tri, d_cl;
+  ClrArgs g = m->base;
+  g.max_dist2 = max_dist * max_dist;
+  g.pos = view.pos; g.anchor_xy = view.pos_anchor_xy; g.stride = view.stride; g.first = first; g.count = count; g.elem_size = view.state_elem_size;
+  g.out_stride = count;
+  if (out_is_device) {
+    g.dist2_out = (double *)dist2_out; g.tri_out = (int32_t *)tri_out; g.closest_out = (double *)closest_out;
+  } else {
+    if (!d_d2.alloc(n * 8) || !d_tri.alloc(n * 4) || (closest_out && !d_cl.alloc(n * 24))) { (void)hipGetLastError(); return AFE_ERR_HIP; }
+    g.dist2_out = (double *)d_d2.p; g.tri_out = (int32_t *)d_tri.p; g.closest_out = (double *)d_cl.p;
+  }
+  float ms = 0;
+  rc = launch_query<false, false>(g, stream, &ms);     // synchronises (timing)
+  if (rc != AFE_OK) return rc;
+  if (kernel_ms) *kernel_ms = ms;
+  if (!out_is_device &&
+      (hipMemcpy(dist2_out, d_d2.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tri_out, d_tri.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+       (closest_out && hipMemcpy(closest_out, d_cl.p, n * 24, hipMemcpyDeviceToHost) != hipSuccess)))
+    return AFE_ERR_HIP;
+  return AFE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the contact monitor
+// ---------------------------------------------------------------------------------------
+namespace {
+int monitor_reset_range(afe_contact_monitor *c, int64_t first, int64_t count, hipStream_t stream) {
+  for (int64_t done = 0; done < count; done += kPointsPerLaunch) {
+    const int64_t n = std::min(count - done, kPointsPerLaunch);
+    hipLaunchKernelGGL(afe_clearance_reset_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, c->min_dist2, c->first_us,
+                       c->first_tri, first + done, n);
+    if (hipGetLastError() != hipSuccess) return AFE_ERR_HIP;
+  }
+  return AFE_OK;
+}
+}  // namespace
+
+extern "C" int afe_contact_monitor_create(afe_engine *e, afe_clearance_map *m, double contact_radius, double search_radius,
+                                          afe_contact_monitor **out) {
+  if (!e || !m || !out) return AFE_ERR_INVALID_ARG;
+  if (!(contact_radius > 0.0) || !(contact_radius <= search_radius) || !std::isfinite(search_radius)) return AFE_ERR_INVALID_ARG;
+  hipStream_t stream = nullptr;
+  int device = 0;
+  afe::engine_stream_device(e, (void **)&stream, &device);
+  if (device != m->device) return AFE_ERR_INVALID_ARG;
+  afe_device_view view;
+  view.struct_bytes = sizeof(view);
+  int rc = afe::engine_device_view(e, &view);
+  if (rc != AFE_OK) return rc;
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  afe_contact_monitor *c = new afe_contact_monitor();
+  c->engine = e; c->map = m; c->n = view.n_vehicles; c->device = device;
+  c->contact2 = contact_radius * contact_radius;
+  c->search2 = search_radius * search_radius;
+  const size_t n = (size_t)c->n;
+  if (hipMalloc((void **)&c->min_dist2, n * 8) != hipSuccess || hipMalloc((void **)&c->first_us, n * 8) != hipSuccess ||
+      hipMalloc((void **)&c->first_tri, n * 4) != hipSuccess || hipMalloc((void **)&c->counts, 16) != hipSuccess ||
+      hipHostMalloc((void **)&c->counts_host, 16, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)afe_contact_monitor_destroy(c);
+    return AFE_ERR_HIP;
+  }
+  rc = monitor_reset_range(c, 0, c->n, stream);
+  if (rc == AFE_OK && hipStreamSynchronize(stream) != hipSuccess) rc = AFE_ERR_HIP;
+  if (rc != AFE_OK) { (void)afe_contact_monitor_destroy(c); return rc; }
+  *out = c;
+  return AFE_OK;
+}
+
+extern "C" int afe_contact_monitor_update(afe_contact_monitor *c, int64_t *n_in_contact, int64_t *n_ever_in_contact) {
+  if (!c) return AFE_ERR_INVALID_ARG;
+  hipStream_t stream = nullptr;
+  int device = 0;
+  afe::engine_stream_device(c->engine, (void **)&stream, &device);
+  afe_device_view view;
+  view.struct_bytes = sizeof(view);
+  int rc = afe::engine_device_view(c->engine, &view);
+  if (rc != AFE_OK) return rc;
+  if (view.n_vehicles != c->n) return AFE_ERR_INVALID_ARG;
+  uint64_t now_us = 0;
+  rc = afe_time_us(c->engine, &now_us);
+  if (rc != AFE_OK) return rc;
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  ClrArgs g = c->map->base;
+  g.max_dist2 = c->search2;
+  g.pos = view.pos; g.anchor_xy = view.pos_anchor_xy; g.stride = view.stride; g.first = 0; g.count = c->n; g.elem_size = view.state_elem_size;
+  g.min_dist2 = c->min_dist2; g.first_us = c->first_us; g.first_tri = c->first_tri; g.counts = c->counts;
+  g.contact2 = c->contact2; g.now_us = now_us;
+  if (hipMemsetAsync(c->counts, 0, 16, stream) != hipSuccess) return AFE_ERR_HIP;
+  rc = launch_query<true, false>(g, stream, nullptr);
+  if (rc != AFE_OK) return rc;
+  // the only bytes that cross the bus: one 16-byte copy
+  if (hipMemcpyAsync(c->counts_host, c->counts, 16, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+    return AFE_ERR_HIP;
+  if (n_in_contact) *n_in_contact = (int64_t)c->counts_host[0];
+  if (n_ever_in_contact) *n_ever_in_contact = (int64_t)c->counts_host[1];
+  return AFE_OK;
+}
+
+extern "C" int afe_contact_monitor_get(afe_contact_monitor *c, int64_t first, int64_t count, double *min_dist2, uint64_t *first_contact_us,
+                                       int32_t *first_contact_tri) {
+  if (!c || first < 0 || count < 0) return AFE_ERR_INVALID_ARG;
+  if (first > c->n || count > c->n - first) return AFE_ERR_OUT_OF_RANGE;
+  if (count == 0) return AFE_OK;
+  hipStream_t stream = nullptr;
+  int device = 0;
+  afe::engine_stream_device(c->engine, (void **)&stream, &device);
+  if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return AFE_ERR_HIP;
+  const size_t n = (size_t)count;
+  if ((min_dist2 && hipMemcpy(min_dist2, c->min_dist2 + first, n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (first_contact_us && hipMemcpy(first_contact_us, c->first_us + first, n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (first_contact_tri && hipMemcpy(first_contact_tri, c->first_tri + first, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+    return AFE_ERR_HIP;
+  return AFE_OK;
+}
+
+extern "C" int afe_contact_monitor_reset(afe_contact_monitor *c, int64_t first, int64_t count) {
+  if (!c || first < 0 || count < 0) return AFE_ERR_INVALID_ARG;
+  if (first > c->n || count > c->n - first) return AFE_ERR_OUT_OF_RANGE;
+  if (count == 0) return AFE_OK;
+  hipStream_t stream = nullptr;
+  int device = 0;
+  afe::engine_stream_device(c->engine, (void **)&stream, &device);
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  return monitor_reset_range(c, first, count, stream);
+}
+
+extern "C" int afe_contact_monitor_destroy(afe_contact_monitor *c) {
+  if (!c) return AFE_ERR_INVALID_ARG;
+  (void)hipSetDevice(c->device);
+  (void)hipDeviceSynchronize();
+  if (c->min_dist2) (void)hipFree(c->min_dist2);
+  if (c->first_us) (void)hipFree(c->first_us);
+  if (c->first_tri) (void)hipFree(c->first_tri);
+  if (c->counts) (void)hipFree(c->counts);
+  if (c->counts_host) (void)hipHostFree(c->counts_host);
+  delete c;
+  return AFE_OK;
+}

@@ -49,6 +49,10 @@ ABI_FUNCTIONS = [
     "afe_set_noise_seed", "afe_set_gust_process", "afe_get_external_force", "afe_nearest_neighbour_async", "afe_query_sync",
     "afe_gather_exchange", "afe_set_cache_policy", "afe_grid_time", "afe_cache_policy_in_use", "afe_set_resident_queue",
     "afe_has_dev_hooks", "afe_persistent_kernarg_layout", "afe_group_set_staged_copies",
+    "afe_clearance_map_create", "afe_clearance_map_destroy", "afe_clearance_map_info", "afe_clearance_check_hierarchy",
+    "afe_clearance_query", "afe_clearance_query_stats", "afe_clearance_query_engine",
+    "afe_contact_monitor_create", "afe_contact_monitor_update", "afe_contact_monitor_get", "afe_contact_monitor_reset",
+    "afe_contact_monitor_destroy",
 ]
 
 
@@ -362,6 +366,18 @@ def library():
         "afe_uwb_set_noise": [vp, C.c_double, C.c_double, C.c_double],
         "afe_uwb_draw": [vp, i64, vp, vp],
         "afe_uwb_range": [vp, eng, vp, i64, vp, vp, i64, vp, vp],
+        "afe_clearance_map_create": [ci, vp, i64, C.POINTER(vp)],
+        "afe_clearance_map_destroy": [vp],
+        "afe_clearance_map_info": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), vp],
+        "afe_clearance_check_hierarchy": [vp, i64, C.POINTER(i64), C.POINTER(ci), C.POINTER(ci)],
+        "afe_clearance_query": [vp, i64, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_float)],
+        "afe_clearance_query_stats": [vp, i64, vp, C.c_double, vp, C.POINTER(C.c_float)],
+        "afe_clearance_query_engine": [eng, vp, i64, i64, C.c_double, vp, vp, vp, ci, C.POINTER(C.c_float)],
+        "afe_contact_monitor_create": [eng, vp, C.c_double, C.c_double, C.POINTER(vp)],
+        "afe_contact_monitor_update": [vp, C.POINTER(i64), C.POINTER(i64)],
+        "afe_contact_monitor_get": [vp, i64, i64, vp, vp, vp],
+        "afe_contact_monitor_reset": [vp, i64, i64],
+        "afe_contact_monitor_destroy": [vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -621,6 +637,131 @@ def scene_check_hierarchy(triangles):
     if rc:
         raise AfeError(rc, library().afe_status_string(rc).decode())
     return nn.value, d.value, ml.value
+
+
+def _status(rc):
+    if rc:
+        raise AfeError(rc, library().afe_status_string(rc).decode())
+
+
+class ClearanceMap:
+    """afe_clearance_map: a static triangle mesh (world frame, metres) + its own hierarchy in HBM, answering
+    "how far is this point from the mesh" (squared distances; see the header)."""
+
+    def __init__(self, triangles, device=-1):
+        t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+        self._h = C.c_void_p()
+        _status(library().afe_clearance_map_create(int(device), t.ctypes.data, t.shape[0], C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_clearance_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        nt, nn, d = C.c_int64(), C.c_int64(), C.c_int()
+        b = np.empty(6)
+        _status(library().afe_clearance_map_info(self._h, C.byref(nt), C.byref(nn), C.byref(d), b.ctypes.data))
+        return {"n_tri": nt.value, "n_nodes": nn.value, "depth": d.value, "bounds": b}
+
+    def query(self, pos, max_dist=np.inf, want_closest=True):
+        """pos [3, n] -> (dist2 [n], tri [n] int32, closest [3, n] or None, kernel_ms)."""
+        p = np.ascontiguousarray(pos, dtype=np.float64)
+        n = p.shape[1]
+        assert p.shape == (3, n)
+        d2, tri = np.empty(n), np.empty(n, np.int32)
+        cl = np.empty((3, n)) if want_closest else None
+        ms = C.c_float(0)
+        _status(library().afe_clearance_query(self._h, n, p.ctypes.data, float(max_dist), d2.ctypes.data, tri.ctypes.data,
+                                              None if cl is None else cl.ctypes.data, C.byref(ms)))
+        return d2, tri, cl, ms.value
+
+    def query_stats(self, pos, max_dist=np.inf):
+        """traversal counters of one batch (counting build), summed over the points: dict + kernel_ms"""
+        p = np.ascontiguousarray(pos, dtype=np.float64)
+        st = np.zeros(4, np.uint64)
+        ms = C.c_float(0)
+        _status(library().afe_clearance_query_stats(self._h, p.shape[1], p.ctypes.data, float(max_dist), st.ctypes.data, C.byref(ms)))
+        return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "points"), (int(x) for x in st))), ms.value
+
+    def query_engine(self, ensemble, max_dist, first=0, count=None, out=None):
+        """The same for vehicles [first, first+count) from the engine's device state.  out: None to get
+        (dist2, tri, closest, kernel_ms) on the host, or a (dist2, tri, closest) tuple of DeviceBuffers (closest may
+        be None) to keep the answers in HBM (returns kernel_ms only)."""
+        count = ensemble.n - first if count is None else count
+        ms = C.c_float(0)
+        if out is None:
+            d2, tri, cl = np.empty(max(count, 0)), np.empty(max(count, 0), np.int32), np.empty((3, max(count, 0)))
+            args, is_dev = (d2.ctypes.data, tri.ctypes.data, cl.ctypes.data), 0
+        else:
+            b_d2, b_tri, b_cl = out
+            assert b_d2.nbytes >= count * 8 and b_tri.nbytes >= count * 4 and (b_cl is None or b_cl.nbytes >= count * 24)
+            args, is_dev = (b_d2.ptr, b_tri.ptr, None if b_cl is None else b_cl.ptr), 1
+        _status(library().afe_clearance_query_engine(ensemble.handle, self._h, int(first), int(count), float(max_dist),
+                                                     args[0], args[1], args[2], is_dev, C.byref(ms)))
+        return (d2, tri, cl, ms.value) if out is None else ms.value
+
+
+def clearance_check_hierarchy(triangles):
+    """Host-only: (n_nodes, depth, max_leaf) of the clearance hierarchy for a mesh, after verifying its invariants."""
+    t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    nn, d, ml = C.c_int64(), C.c_int(), C.c_int()
+    _status(library().afe_clearance_check_hierarchy(t.ctypes.data, t.shape[0], C.byref(nn), C.byref(d), C.byref(ml)))
+    return nn.value, d.value, ml.value
+
+
+class ContactMonitor:
+    """afe_contact_monitor: per-vehicle closest approach and first contact, latched on the device.  Borrows the
+    ensemble and the map: close it before either of them."""
+
+    NEVER = np.uint64(0xffffffffffffffff)
+
+    def __init__(self, ensemble, cmap, contact_radius, search_radius):
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = (ensemble, cmap)
+        _status(library().afe_contact_monitor_create(ensemble.handle, cmap.handle, float(contact_radius), float(search_radius),
+                                                     C.byref(self._h)))
+
+    def update(self):
+        """-> (vehicles in contact now, vehicles ever in contact)"""
+        now, ever = C.c_int64(), C.c_int64()
+        _status(library().afe_contact_monitor_update(self._h, C.byref(now), C.byref(ever)))
+        return now.value, ever.value
+
+    def get(self, first=0, count=None):
+        """-> dict(min_dist2 [count], first_contact_us [count] uint64 (NEVER: none), first_contact_tri [count] int32 (-1))"""
+        count = self.n - first if count is None else count
+        out = dict(min_dist2=np.empty(count), first_contact_us=np.empty(count, np.uint64), first_contact_tri=np.empty(count, np.int32))
+        _status(library().afe_contact_monitor_get(self._h, int(first), int(count), out["min_dist2"].ctypes.data,
+                                                  out["first_contact_us"].ctypes.data, out["first_contact_tri"].ctypes.data))
+        return out
+
+    def reset(self, first=0, count=None):
+        count = self.n - first if count is None else count
+        _status(library().afe_contact_monitor_reset(self._h, int(first), int(count)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_contact_monitor_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def type_from_id(vehicle_id):

@@ -424,6 +424,72 @@ int afe_render_depth_stats(afe_scene *s, const afe_camera *cam, int64_t n_views,
 int afe_render_depth_engine(afe_engine *e, afe_scene *s, const afe_camera *cam, int64_t first, int64_t count,
                             const double mount[4], void *depth_out, int out_is_device, float *kernel_ms);
 
+/* ---- mesh clearance and contact monitor -----------------------------------
+ * What the reference left to Unity's collision report: how close is every
+ * vehicle to the world's triangle mesh, and has it touched it?  A clearance
+ * map is a static mesh (world frame, metres) with a hierarchy of its own in
+ * HBM -- a second handle beside afe_scene for the same triangles: the camera's
+ * tree is laid out for coherent rays, this one for one incoherent point per
+ * lane.  Distances are returned SQUARED (the definition uses + - * / only, so
+ * that every bit of the answer is specified: csrc/afe_clearance.hip states the
+ * expression tree).  The vehicle is a point: compare with the square of its
+ * radius.  Contact is reported, the physics does not react to it.
+ * Not covered: swept tests between two queries.  A monitor updated at 100 Hz
+ * sees a vehicle at the planner's 5 m/s limit every 5 cm, against a vehicle
+ * radius of 11.6 cm; thinner obstacles or faster vehicles need a higher rate. */
+typedef struct afe_clearance_map afe_clearance_map;
+/* triangles: n_tri x 9 floats (v0, v1, v2), finite.  device < 0: current device. */
+int afe_clearance_map_create(int device, const float *triangles, int64_t n_tri, afe_clearance_map **out);
+/* NULL is AFE_ERR_INVALID_ARG.  Destroy the monitors that borrow the map first. */
+int afe_clearance_map_destroy(afe_clearance_map *m);
+/* n_tri, inner nodes of the hierarchy, its depth, world bounds {min xyz, max xyz} */
+int afe_clearance_map_info(const afe_clearance_map *m, int64_t *n_tri, int64_t *n_nodes, int *depth, double bounds[6]);
+/* Pure host (no GPU): builds the hierarchy afe_clearance_map_create would build and verifies it -- every triangle
+ * in exactly one leaf (or once in the short list of scene-spanning triangles kept out of the tree), every box
+ * containing what hangs below it, depth within the traversal stack (32); leaves hold at most 4 triangles. */
+int afe_clearance_check_hierarchy(const float *triangles, int64_t n_tri, int64_t *n_nodes, int *depth, int *max_leaf);
+
+/* Explicit points: pos planar [3][n_points] doubles.  Per point: squared distance to the closest point of the mesh,
+ * index of that triangle IN THE ORDER GIVEN TO afe_clearance_map_create (lowest index among bitwise-equal distances),
+ * and (closest_out != NULL) the closest point, planar [3][n_points].  Only triangles with dist2 <= max_dist*max_dist
+ * count (product formed once, in double); a point with none gets dist2 = +inf, index -1, closest = NaN.
+ * max_dist = +inf is allowed (plain nearest-triangle query); NaN or <= 0 is AFE_ERR_INVALID_ARG.  A point with a
+ * non-finite coordinate is answered +inf / -1 without a walk.  kernel_ms (optional): HIP-event time of the launch. */
+int afe_clearance_query(afe_clearance_map *m, int64_t n_points, const double *pos, double max_dist,
+                        double *dist2_out, int32_t *tri_out, double *closest_out, float *kernel_ms);
+/* What the traversal did for such a batch (a counting build of the same kernel; the answers are discarded), summed
+ * over the points: stats[0] tree nodes visited, [1] triangle box tests, [2] double-precision closest-point
+ * evaluations, [3] points. */
+int afe_clearance_query_stats(afe_clearance_map *m, int64_t n_points, const double *pos, double max_dist,
+                              uint64_t stats[4], float *kernel_ms);
+/* The same query for vehicles [first, first+count) read on the device from the engine's slabs (fp32 or fp64 state;
+ * absolute x = pos_anchor_xy + (double)pos, as the depth camera forms it), ordered on the engine's stream; a
+ * resident step grid ends first.  Outputs (dist2: count doubles, tri: count int32, closest: planar [3][count]
+ * doubles or NULL) are DEVICE pointers when out_is_device != 0, else host buffers.  Engine and map must live on
+ * the same device.  count == 0 with a valid range returns AFE_OK without touching the engine. */
+int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t count, double max_dist,
+                               void *dist2_out, void *tri_out, void *closest_out, int out_is_device, float *kernel_ms);
+
+/* Per-vehicle latches, device resident, for a closed loop that wants to know about contact without downloading
+ * the state: 0 < contact_radius <= search_radius, both finite.  The monitor BORROWS engine and map: destroy it
+ * before either of them (not tracked). */
+typedef struct afe_contact_monitor afe_contact_monitor;
+int afe_contact_monitor_create(afe_engine *e, afe_clearance_map *m, double contact_radius, double search_radius,
+                               afe_contact_monitor **out);
+/* One query (max_dist = search_radius) at the engine's current state and time (afe_time_us); updates, per vehicle:
+ * the smallest dist2 seen so far over the updates (+inf while nothing came within search_radius), and -- the first
+ * time dist2 <= contact_radius^2 -- the time and the triangle index of that update.  Returns how many vehicles
+ * are in contact now and how many ever were: two integers summed on the device, the only bytes that cross the
+ * bus.  Nothing is allocated here. */
+int afe_contact_monitor_update(afe_contact_monitor *c, int64_t *n_in_contact, int64_t *n_ever_in_contact);
+/* the latches of vehicles [first, first+count) (any output may be NULL): first_contact_us is UINT64_MAX and
+ * first_contact_tri -1 for a vehicle that never made contact */
+int afe_contact_monitor_get(afe_contact_monitor *c, int64_t first, int64_t count, double *min_dist2,
+                            uint64_t *first_contact_us, int32_t *first_contact_tri);
+/* back to "nothing seen" for vehicles [first, first+count) */
+int afe_contact_monitor_reset(afe_contact_monitor *c, int64_t first, int64_t count);
+int afe_contact_monitor_destroy(afe_contact_monitor *c);   /* NULL is AFE_ERR_INVALID_ARG */
+
 /* Device scratch helpers for hosts without their own HIP allocator (ctypes). */
 int afe_device_alloc(int device, uint64_t bytes, void **out);
 int afe_device_free(void *p);
