@@ -1,6 +1,8 @@
 // afe_engine.cpp -- host side of the C ABI (include/agrifly_engine.h): owns the
 // SoA slabs in HBM, the engine clock and the logic-gate plan, and launches the
-// kernels of afe_kernels.hip.  Compiled with hipcc; there is no CPU fallback.
+// kernels of afe_kernels.hip.  Compiled with hipcc; there is no CPU fallback.  The resident grid's lifecycle (running ->
+// parked -> collected -> relaunched, or failed) has one writer per fact: grid_failed latches a failure, main_stream is
+// the gate every call passes before it touches the stream or the slabs, persist_take_over follows a grid that left.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -108,9 +110,16 @@ struct afe_engine {
 
   // persistent stepping (afe_set_step_mode; afe_device.h PersistArgs)
   int step_mode = AFE_STEP_LAUNCH;
-  bool p_running = false;   // a resident grid is on the device
-  bool p_failed = false;    // a resident grid gave up: the ensemble may be torn between two steps, stepping is refused
-  std::string p_fail_msg;   // what it said when it did (kept apart from err, which every later refusal rewrites)
+  // The lifecycle of the resident grid.  Only the persist_* functions, quiesce and grid_failed write these; each by:
+  bool p_running = false;   // a resident grid is on the device: persist_launch sets, persist_collect clears
+  bool p_failed = false;    // a resident grid gave up: the ensemble may be torn between two steps, every call is refused: grid_failed alone
+  std::string p_fail_msg;   // what the first failure said (kept apart from err, which every later call rewrites): grid_failed alone
+  uint64_t p_next = 0;      // ring entries written so far == index of the next step to authorise: persist_step
+  uint64_t p_resume = 0;    // where the next grid starts (every worker's done[] stands there while none runs): persist_collect
+  bool p_on_aql = false;            // the grid now resident was dispatched on the engine's own queue: persist_launch sets, persist_collect clears
+  uint64_t p_launch_start = 0;      // the step the grid now resident started from: persist_launch
+  uint64_t p_quiesced = 0;          // every step below this index is known to be done (the last successful wait): quiesce
+  uint64_t p_sync_posted = 0;       // 1 + the step count of the sync request posted to the grid now resident (0: none): quiesce posts, persist_launch and grid_failed withdraw
   unsigned long long *p_host = nullptr;      // pinned host memory: ring[AFE_PERSIST_HOST_RING] + status[8]
   unsigned long long *p_host_dev = nullptr;  // the same memory as the device addresses it
   unsigned long long *p_dev = nullptr;       // device memory: ring[AFE_PERSIST_DEV_RING] + done[p_workers]
@@ -121,8 +130,6 @@ struct afe_engine {
   int p_capacity = 0;       // resident one-wave workgroups per CU of the current configuration's kernel (p_capacity_key)
   unsigned p_capacity_key = 0;
   bool p_balanced = false;
-  uint64_t p_next = 0;      // ring entries written so far == index of the next step to authorise
-  uint64_t p_resume = 0;    // where the next grid starts (every worker's done[] stands there while none runs)
   uint64_t p_dt_us = 0;     // what the resident grid was launched with
   unsigned p_epoch = 0;     // launches so far
   uint64_t p_seg_start = 0, p_seg_t0_us = 0, p_seg_gust_applied = ~0ull;   // the current run of equally long steps: its first index, the engine time and the slab's gust epoch there
@@ -132,29 +139,27 @@ struct afe_engine {
   afe::AqlQueue *aql = nullptr;
   bool aql_tried = false;
   int aql_mode = -1;                // afe_set_resident_queue: -1 automatic (by size), 0 the HIP stream, 1 the engine's own queue
-  bool p_on_aql = false;            // the grid now resident was dispatched there
   std::map<unsigned, afe::AqlKernel> aql_kernels;    // by configuration key (persist_size_grid's) | precision << 8
   bool view_exported = false;       // afe_get_device_view has handed the slabs to somebody: afe_sync must leave them readable
   uint64_t p_grid_ns = 0, p_grid_steps = 0;          // device time and steps of the grids collected so far (afe_grid_time)
-  uint64_t p_launch_start = 0;                       // the step the grid now resident started from
   bool p_prio = false;                               // the grid now resident balances its workers by issue priority (persist_launch)
-  uint64_t p_quiesced = 0;                           // every step below this index is known to be done (the last successful wait)
-  uint64_t p_sync_posted = 0;                        // 1 + the step count of the sync request posted to the grid now resident (0: none)
 
   std::string err;
 };
 
 namespace {
-void join_streams(afe_engine *e);
-hipStream_t main_stream(afe_engine *e);
-int persist_park(afe_engine *e);
+int main_stream(afe_engine *e);
 int quiesce(afe_engine *e);
-int gust_resample(afe_engine *e, uint64_t epoch);
-}  // namespace
-
-namespace {
 
 inline size_t elem(const afe_engine *e) { return e->precision == AFE_F64 ? 8 : 4; }
+
+// what differs between the fp32 and the fp64 engine besides the type: the host copy of the table and the launchers
+inline std::vector<DevParams<float>> &host_table(afe_engine *e, float) { return e->table_f32; }
+inline std::vector<DevParams<double>> &host_table(afe_engine *e, double) { return e->table_f64; }
+inline int launch_step(const StepView<float> &v, const LaunchFlags &f, const DevParams<float> *u, const DevLogic *l, void *st) { return launch_step_f32(v, f, u, l, st); }
+inline int launch_step(const StepView<double> &v, const LaunchFlags &f, const DevParams<double> *u, const DevLogic *l, void *st) { return launch_step_f64(v, f, u, l, st); }
+inline int launch_persistent(const StepView<float> &v, const LaunchFlags &f, const DevParams<float> &u, const DevLogic *l, const PersistArgs &a, void *st) { return launch_persistent_f32(v, f, u, l, a, st); }
+inline int launch_persistent(const StepView<double> &v, const LaunchFlags &f, const DevParams<double> &u, const DevLogic *l, const PersistArgs &a, void *st) { return launch_persistent_f64(v, f, u, l, a, st); }
 
 int fail(afe_engine *e, int status, const std::string &msg) {
   if (e) e->err = msg;
@@ -200,11 +205,11 @@ int copy_in(afe_engine *e, void *dev, size_t esz, int comps, int64_t first, int6
     __atomic_thread_fence(__ATOMIC_RELEASE);   // ahead of the ring entry / the launch that lets the device read it
     return AFE_OK;
   }
-  hipStream_t st = main_stream(e);                   // (ends a resident grid)
-  if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);   // a grid that gave up or did not come back: the ensemble may be torn, nothing is written over it
+  const int rc = main_stream(e);                     // (ends a resident grid; after one that failed the ensemble may be torn: nothing is written over it)
+  if (rc) return rc;
   AFE_HIP(e, hipMemcpy2DAsync((char *)dev + first * esz, e->stride * esz, host, count * esz,
-                              count * esz, comps, hipMemcpyHostToDevice, st));
-  AFE_HIP(e, hipStreamSynchronize(st));              // host buffer may be reused by the caller
+                              count * esz, comps, hipMemcpyHostToDevice, e->stream));
+  AFE_HIP(e, hipStreamSynchronize(e->stream));       // host buffer may be reused by the caller
   return AFE_OK;
 }
 int copy_out(afe_engine *e, const void *dev, size_t esz, int comps, int64_t first, int64_t count, void *host) {
@@ -217,11 +222,11 @@ int copy_out(afe_engine *e, const void *dev, size_t esz, int comps, int64_t firs
       std::memcpy((char *)host + (size_t)c * count * esz, d + ((size_t)c * e->stride + first) * esz, (size_t)count * esz);
     return AFE_OK;
   }
-  hipStream_t st = main_stream(e);                   // (ends a resident grid)
-  if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);   // ... and a torn ensemble is not handed out as a state
+  const int rc = main_stream(e);                     // (... and a torn ensemble is not handed out as a state)
+  if (rc) return rc;
   AFE_HIP(e, hipMemcpy2DAsync(host, count * esz, (const char *)dev + first * esz, e->stride * esz,
-                              count * esz, comps, hipMemcpyDeviceToHost, st));
-  AFE_HIP(e, hipStreamSynchronize(st));
+                              count * esz, comps, hipMemcpyDeviceToHost, e->stream));
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
   return AFE_OK;
 }
 
@@ -236,7 +241,9 @@ int fill_rows(afe_engine *e, void *dev, size_t esz, int comps, int64_t first, in
     __atomic_thread_fence(__ATOMIC_RELEASE);
     return AFE_OK;
   }
-  AFE_HIP(e, hipMemset2DAsync((char *)dev + first * esz, e->stride * esz, byte, count * esz, comps, main_stream(e)));
+  const int rc = main_stream(e);
+  if (rc) return rc;
+  AFE_HIP(e, hipMemset2DAsync((char *)dev + first * esz, e->stride * esz, byte, count * esz, comps, e->stream));
   return AFE_OK;
 }
 
@@ -257,6 +264,16 @@ int get_field(afe_engine *e, const void *dev, int comps, int64_t first, int64_t 
   if (rc) return rc;
   for (size_t k = 0; k < tmp.size(); k++) host[k] = (Dst)tmp[k];
   return AFE_OK;
+}
+
+// ... to and from a slab of the engine's own precision
+template <typename H>
+int set_real(afe_engine *e, void *dev, int comps, int64_t first, int64_t count, const H *host) {
+  return e->precision == AFE_F64 ? set_field<double>(e, dev, comps, first, count, host) : set_field<float>(e, dev, comps, first, count, host);
+}
+template <typename H>
+int get_real(afe_engine *e, const void *dev, int comps, int64_t first, int64_t count, H *host) {
+  return e->precision == AFE_F64 ? get_field<double>(e, dev, comps, first, count, host) : get_field<float>(e, dev, comps, first, count, host);
 }
 
 int materialize_motor(afe_engine *e);   // defined below
@@ -318,22 +335,12 @@ int set_state_any(afe_engine *e, int64_t first, int64_t count, const H *pos3, co
                   const H *att4, const H *ang_vel3, const H *motor4) {
   int rc = check_range(e, first, count);
   if (rc) return rc;
-  AFE_HIP(e, hipSetDevice(e->device));
   if (motor4 && (rc = materialize_motor(e))) return rc;   // the rest of the slab must be current
-  if (e->precision == AFE_F64) {
-    if ((rc = set_positions(e, first, count, pos3))) return rc;
-    if ((rc = set_field<double>(e, e->vel, 3, first, count, vel3))) return rc;
-    if ((rc = set_field<double>(e, e->att, 4, first, count, att4))) return rc;
-    if ((rc = set_field<double>(e, e->ang_vel, 3, first, count, ang_vel3))) return rc;
-    if ((rc = set_field<double>(e, e->motor, 4, first, count, motor4))) return rc;
-  } else {
-    if ((rc = set_positions(e, first, count, pos3))) return rc;
-    if ((rc = set_field<float>(e, e->vel, 3, first, count, vel3))) return rc;
-    if ((rc = set_field<float>(e, e->att, 4, first, count, att4))) return rc;
-    if ((rc = set_field<float>(e, e->ang_vel, 3, first, count, ang_vel3))) return rc;
-    if ((rc = set_field<float>(e, e->motor, 4, first, count, motor4))) return rc;
-  }
-  return AFE_OK;
+  if ((rc = set_positions(e, first, count, pos3))) return rc;
+  if ((rc = set_real(e, e->vel, 3, first, count, vel3))) return rc;
+  if ((rc = set_real(e, e->att, 4, first, count, att4))) return rc;
+  if ((rc = set_real(e, e->ang_vel, 3, first, count, ang_vel3))) return rc;
+  return set_real(e, e->motor, 4, first, count, motor4);
 }
 
 template <typename H>
@@ -341,53 +348,36 @@ int get_state_any(afe_engine *e, int64_t first, int64_t count, H *pos3, H *vel3,
                   H *ang_vel3, H *motor4) {
   int rc = check_range(e, first, count);
   if (rc) return rc;
-  AFE_HIP(e, hipSetDevice(e->device));
   if (motor4 && (rc = materialize_motor(e))) return rc;
-  if (e->precision == AFE_F64) {
-    if ((rc = get_positions(e, first, count, pos3))) return rc;
-    if ((rc = get_field<double>(e, e->vel, 3, first, count, vel3))) return rc;
-    if ((rc = get_field<double>(e, e->att, 4, first, count, att4))) return rc;
-    if ((rc = get_field<double>(e, e->ang_vel, 3, first, count, ang_vel3))) return rc;
-    if ((rc = get_field<double>(e, e->motor, 4, first, count, motor4))) return rc;
-  } else {
-    if ((rc = get_positions(e, first, count, pos3))) return rc;
-    if ((rc = get_field<float>(e, e->vel, 3, first, count, vel3))) return rc;
-    if ((rc = get_field<float>(e, e->att, 4, first, count, att4))) return rc;
-    if ((rc = get_field<float>(e, e->ang_vel, 3, first, count, ang_vel3))) return rc;
-    if ((rc = get_field<float>(e, e->motor, 4, first, count, motor4))) return rc;
-  }
-  return AFE_OK;
+  if ((rc = get_positions(e, first, count, pos3))) return rc;
+  if ((rc = get_real(e, e->vel, 3, first, count, vel3))) return rc;
+  if ((rc = get_real(e, e->att, 4, first, count, att4))) return rc;
+  if ((rc = get_real(e, e->ang_vel, 3, first, count, ang_vel3))) return rc;
+  return get_real(e, e->motor, 4, first, count, motor4);
 }
 
 int set_wrench(afe_engine *e, void *dev, bool &flag, int64_t first, int64_t count, const double *w3) {
   int rc = check_range(e, first, count);
   if (rc) return rc;
-  AFE_HIP(e, hipSetDevice(e->device));
-  if (!w3) {
-    return fill_rows(e, dev, elem(e), 3, first, count, 0);
-  }
+  if (!w3) return fill_rows(e, dev, elem(e), 3, first, count, 0);
   flag = true;
-  if (e->precision == AFE_F64) return set_field<double>(e, dev, 3, first, count, w3);
-  return set_field<float>(e, dev, 3, first, count, w3);
+  return set_real(e, dev, 3, first, count, w3);
 }
 
 // (re)build the device type table when the table or dt changed
+template <typename R>
+int upload_table(afe_engine *e, double dt) {
+  std::vector<DevParams<R>> &t = host_table(e, R());
+  t.resize(e->table.size());
+  for (size_t k = 0; k < t.size(); k++) to_device_params<R>(e->table[k], dt, t[k]);
+  AFE_HIP(e, hipMemcpyAsync(e->dev_table, t.data(), t.size() * sizeof(t[0]), hipMemcpyHostToDevice, e->stream));
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
+  return AFE_OK;
+}
 int refresh_table(afe_engine *e, double dt) {
   if (!e->table_dirty && dt == e->table_dt) return AFE_OK;
-  const size_t n = e->table.size();
-  if (e->precision == AFE_F64) {
-    std::vector<DevParams<double>> &t = e->table_f64;
-    t.resize(n);
-    for (size_t k = 0; k < n; k++) to_device_params<double>(e->table[k], dt, t[k]);
-    AFE_HIP(e, hipMemcpyAsync(e->dev_table, t.data(), n * sizeof(t[0]), hipMemcpyHostToDevice, main_stream(e)));
-    AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
-  } else {
-    std::vector<DevParams<float>> &t = e->table_f32;
-    t.resize(n);
-    for (size_t k = 0; k < n; k++) to_device_params<float>(e->table[k], dt, t[k]);
-    AFE_HIP(e, hipMemcpyAsync(e->dev_table, t.data(), n * sizeof(t[0]), hipMemcpyHostToDevice, main_stream(e)));
-    AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
-  }
+  int rc = main_stream(e);
+  if (rc || (rc = e->precision == AFE_F64 ? upload_table<double>(e, dt) : upload_table<float>(e, dt))) return rc;
   e->table_dt = dt;
   e->table_dirty = false;
   return AFE_OK;
@@ -404,8 +394,10 @@ int refresh_logic(afe_engine *e) {
     int rc = expand_logic(e->logic_params[k], period, e->logic_table[k], &why);
     if (rc) return fail(e, rc, "logic type " + std::to_string(k) + ": " + why);
   }
-  AFE_HIP(e, hipMemcpyAsync(e->dev_logic_table, e->logic_table.data(), n * sizeof(DevLogic), hipMemcpyHostToDevice, main_stream(e)));
-  AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
+  const int rc = main_stream(e);
+  if (rc) return rc;
+  AFE_HIP(e, hipMemcpyAsync(e->dev_logic_table, e->logic_table.data(), n * sizeof(DevLogic), hipMemcpyHostToDevice, e->stream));
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
   e->logic_table_period = period;
   return AFE_OK;
 }
@@ -424,13 +416,14 @@ bool motor_lazy(const afe_engine *e) { return motors_stateless(e) && !e->logic_o
 // rebuild the rotor-speed slab from the commands of the last step, if it was skipped
 int materialize_motor(afe_engine *e) {
   if (!e->motor_stale) return AFE_OK;
-  AFE_HIP(e, hipSetDevice(e->device));
+  const int rc = main_stream(e);
+  if (rc) return rc;
   // the device table holds the parameters the last step ran with (refresh_table precedes every launch)
   const int lrc = e->precision == AFE_F64
       ? launch_motor_from_cmd_f64((double *)e->motor, e->cmd, e->types_uniform ? nullptr : e->type,
-                                  (const DevParams<double> *)e->dev_table, e->stride, e->n, main_stream(e))
+                                  (const DevParams<double> *)e->dev_table, e->stride, e->n, e->stream)
       : launch_motor_from_cmd_f32((float *)e->motor, e->cmd, e->types_uniform ? nullptr : e->type,
-                                  (const DevParams<float> *)e->dev_table, e->stride, e->n, main_stream(e));
+                                  (const DevParams<float> *)e->dev_table, e->stride, e->n, e->stream);
   if (lrc != 0) return fail(e, AFE_ERR_HIP, std::string("rotor-speed rebuild: ") + hipGetErrorString((hipError_t)lrc));
   e->motor_stale = false;
   return AFE_OK;
@@ -472,15 +465,34 @@ void join_streams(afe_engine *e) {
   if (hipEventRecord(e->ev_side, e->side_stream) == hipSuccess) (void)hipStreamWaitEvent(e->stream, e->ev_side, 0);
   else (void)hipStreamSynchronize(e->side_stream);
 }
-hipStream_t main_stream(afe_engine *e) {
-  join_streams(e);
-  if (e->p_running) (void)persist_park(e);   // a failure is sticky (p_failed) and reported by the next afe_step / afe_sync
-  e->stream_pending = true;                  // whoever asks is about to queue something
-  return e->stream;
-}
 
 // ---- persistent stepping, host side -------------------------------------------------------------------------
 inline volatile unsigned long long *p_status(afe_engine *e) { return e->p_host + AFE_PERSIST_HOST_RING; }
+int persist_park(afe_engine *e);
+
+// The one failure latch of the resident grid: the first message is kept for every later refusal, a posted sync request is
+// withdrawn.  p_running stays as it is (the grid may still be on the device, and afe_destroy needs to know that).
+int grid_failed(afe_engine *e, std::string msg) {
+  if (!e->p_failed) e->p_fail_msg = msg;
+  e->p_failed = true;
+  e->p_sync_posted = 0;
+  return fail(e, AFE_ERR_HIP, msg);
+}
+// ... and the one sticky refusal: it names the original cause whatever e->err has held since
+int refuse_failed(afe_engine *e) {
+  return fail(e, AFE_ERR_HIP, "a persistent step kernel failed earlier (" + e->p_fail_msg + "); create a new engine");
+}
+// The gate to the main stream and the slabs: whoever is about to queue work on e->stream or to read device memory calls it
+// first and goes on only on AFE_OK.  A failed engine is refused before anything is waited for; the side stream is joined;
+// a resident grid ends after its last authorised step.  (afe_step's resident path and afe_destroy do not come through here.)
+int main_stream(afe_engine *e) {
+  AFE_HIP(e, hipSetDevice(e->device));
+  if (e->p_failed) return refuse_failed(e);
+  join_streams(e);
+  const int rc = persist_park(e);
+  e->stream_pending = true;                  // whoever asks is about to queue something
+  return rc;
+}
 
 int persist_alloc(afe_engine *e) {
   if (e->p_host && e->p_host_dev && e->p_dev) return AFE_OK;
@@ -556,9 +568,11 @@ LaunchFlags persist_flags(const afe_engine *e) {
 
 // launch mode: the gust force of `epoch` into the ext_force slab, stream-ordered before the step that needs it
 int gust_resample(afe_engine *e, uint64_t epoch) {
+  const int rc = main_stream(e);             // (the side stream's steps read the slab: joined first)
+  if (rc) return rc;
   const int lrc = e->precision == AFE_F64
-      ? launch_gust_f64((double *)e->ext_force, e->stride, e->n, e->first_global, e->gust_n_global, e->gust_seed, epoch, e->gust_sigma_max, main_stream(e))
-      : launch_gust_f32((float *)e->ext_force, e->stride, e->n, e->first_global, e->gust_n_global, e->gust_seed, epoch, e->gust_sigma_max, main_stream(e));
+      ? launch_gust_f64((double *)e->ext_force, e->stride, e->n, e->first_global, e->gust_n_global, e->gust_seed, epoch, e->gust_sigma_max, e->stream)
+      : launch_gust_f32((float *)e->ext_force, e->stride, e->n, e->first_global, e->gust_n_global, e->gust_seed, epoch, e->gust_sigma_max, e->stream);
   if (lrc != 0) return fail(e, AFE_ERR_HIP, std::string("gust kernel launch: ") + hipGetErrorString((hipError_t)lrc));
   e->gust_applied = epoch;
   return AFE_OK;
@@ -700,6 +714,19 @@ bool aql_launch(afe_engine *e, const afe::AqlKernel &k, const StepView<R> &v, co
   return true;
 }
 
+// the typed end of persist_launch: the view of step p_resume, then the engine's own queue or the HIP stream
+template <typename R>
+int persist_dispatch(afe_engine *e, const afe::AqlKernel *ak, const PersistArgs &a, double dt, uint64_t ticks0, bool *on_aql, int *stream_error) {
+  static const DevLogic no_logic = {};
+  const DevLogic *ulogic = e->logic_on ? &e->logic_table[0] : nullptr;
+  const DevParams<R> &P = host_table(e, R())[0];
+  StepView<R> v;
+  fill_view(e, v);
+  v.dt = (R)dt; v.inv_dt = (R)(1.0 / dt); v.n_steps = 1; v.tick_mask = 0; v.tick_base = ticks0;
+  if (ak) *on_aql = aql_launch(e, *ak, v, P, ulogic ? *ulogic : no_logic, a, stream_error);
+  return *on_aql || *stream_error ? 0 : launch_persistent(v, e->p_flags, P, ulogic, a, e->stream);
+}
+
 int persist_launch(afe_engine *e) {
   volatile unsigned long long *st = p_status(e);
   st[0] = 0; st[1] = e->p_resume; st[2] = 0; st[7] = 0;
@@ -747,23 +774,10 @@ int persist_launch(afe_engine *e) {
   a.gust_epoch_applied = !e->gust_on ? 0 : (e->p_resume > e->p_seg_start ? (t0 - e->p_dt_us) / e->gust_period_us : e->p_seg_gust_applied);
   const double dt = us_to_seconds(e->p_dt_us);
   const LaunchFlags &f = e->p_flags;
-  const DevLogic *ulogic = e->logic_on ? &e->logic_table[0] : nullptr;
-  static const DevLogic no_logic = {};
-  int lrc = 0, stream_error = 0;
+  int stream_error = 0;
   bool on_aql = false;
-  if (e->precision == AFE_F64) {
-    StepView<double> v;
-    fill_view(e, v);
-    v.dt = dt; v.inv_dt = 1.0 / dt; v.n_steps = 1; v.tick_mask = 0; v.tick_base = ticks0;
-    if (ak) on_aql = aql_launch(e, *ak, v, e->table_f64[0], ulogic ? *ulogic : no_logic, a, &stream_error);
-    if (!on_aql && !stream_error) lrc = launch_persistent_f64(v, f, e->table_f64[0], ulogic, a, e->stream);
-  } else {
-    StepView<float> v;
-    fill_view(e, v);
-    v.dt = (float)dt; v.inv_dt = (float)(1.0 / dt); v.n_steps = 1; v.tick_mask = 0; v.tick_base = ticks0;
-    if (ak) on_aql = aql_launch(e, *ak, v, e->table_f32[0], ulogic ? *ulogic : no_logic, a, &stream_error);
-    if (!on_aql && !stream_error) lrc = launch_persistent_f32(v, f, e->table_f32[0], ulogic, a, e->stream);
-  }
+  const int lrc = e->precision == AFE_F64 ? persist_dispatch<double>(e, ak, a, dt, ticks0, &on_aql, &stream_error)
+                                          : persist_dispatch<float>(e, ak, a, dt, ticks0, &on_aql, &stream_error);
   if (stream_error) return fail(e, AFE_ERR_HIP, std::string("engine stream ahead of the resident grid's dispatch: ") + hipGetErrorString((hipError_t)stream_error));
   if (lrc != 0) return fail(e, AFE_ERR_HIP, std::string("persistent step kernel launch: ") + hipGetErrorString((hipError_t)lrc));
   e->p_on_aql = on_aql;
@@ -784,8 +798,8 @@ int persist_collect(afe_engine *e) {
     std::string why;
     const int w = afe_fault("park_timeout") ? 1 : afe::aql_wait(e->aql, 120000000ull, &why);     // (the grid's own patience ends long before: 50 ms without progress)
     if (w != 0) {
-      e->p_running = false; e->p_on_aql = false; e->p_failed = true;
-      return fail(e, AFE_ERR_HIP, "persistent step kernel on the engine's AQL queue: " + (w > 0 ? std::string("still running after 120 s") : why));
+      e->p_running = false; e->p_on_aql = false;
+      return grid_failed(e, "persistent step kernel on the engine's AQL queue: " + (w > 0 ? std::string("still running after 120 s") : why));
     }
     e->p_grid_ns += afe::aql_last_duration_ns(e->aql);
     e->p_on_aql = false;
@@ -816,30 +830,35 @@ int persist_collect(afe_engine *e) {
                  e->p_workers, e->p_shrink_num, (unsigned long long)st[4], (unsigned)(st[5] >> 32), (unsigned)(st[5] & 0xffffffffu),
                  (unsigned long long)st[3], (unsigned long long)(st[6] >> 32));
   } else if (herr != hipSuccess || st[0] == 0 || st[2] != 0) {
-    e->p_failed = true;
-    return fail(e, AFE_ERR_HIP, herr != hipSuccess ? std::string("persistent step kernel: ") + hipGetErrorString(herr)
-                                   : st[2] ? "persistent step kernel gave up waiting (code " + std::to_string(st[2]) + "); the ensemble may be torn between two steps"
-                                           : std::string("persistent step kernel ended without parking"));
+    return grid_failed(e, herr != hipSuccess ? std::string("persistent step kernel: ") + hipGetErrorString(herr)
+                          : st[2] ? "persistent step kernel gave up waiting (code " + std::to_string(st[2]) + "); the ensemble may be torn between two steps"
+                                  : std::string("persistent step kernel ended without parking"));
   }
   else e->p_stall_streak = 0;     // (a grid that parked in the ordinary way)
   e->p_resume = st[0] - 1;
   if (was_aql && e->p_resume >= e->p_launch_start) e->p_grid_steps += e->p_resume - e->p_launch_start;
+  if (e->p_resume > e->p_next) return grid_failed(e, "persistent step kernel ran past the authorised steps");
   return AFE_OK;
+}
+
+// The take-over: collect the grid that has left and, if authorised steps are still waiting (it had parked itself while
+// the host was quiet, or stalled), launch the one that finishes them.  p_running says afterwards which of the two it was.
+int persist_take_over(afe_engine *e) {
+  const int rc = persist_collect(e);
+  if (rc) return rc;
+  return e->p_resume < e->p_next ? persist_launch(e) : AFE_OK;
 }
 
 // End the resident grid after the last authorised step; returns with the stream idle and every step done.
 int persist_park(afe_engine *e) {
   if (!e->p_running) return AFE_OK;
-  (void)hipSetDevice(e->device);
   __atomic_store_n(&e->p_host[e->p_next & (AFE_PERSIST_HOST_RING - 1)], ((e->p_next + 1) << 2) | AFE_PERSIST_PARK, __ATOMIC_RELEASE);
-  for (;;) {
-    int rc = persist_collect(e);
+  // (a loop, not one take-over: a grid launched by it has the park entry ahead of it and is collected in turn)
+  while (e->p_running) {
+    const int rc = persist_take_over(e);
     if (rc) return rc;
-    if (e->p_resume == e->p_next) return AFE_OK;
-    // the grid had parked itself earlier (the host was quiet for a while): a new one finishes the rest
-    if (e->p_resume > e->p_next) { e->p_failed = true; return fail(e, AFE_ERR_HIP, "persistent step kernel ran past the authorised steps"); }
-    if ((rc = persist_launch(e))) return rc;
   }
+  return AFE_OK;
 }
 
 
@@ -847,19 +866,18 @@ int persist_park(afe_engine *e) {
 // read and write the slabs only between seeing a ring entry and publishing their completion mark, and the pump's
 // completion word is written after the marks it summarises: once it stands at p_next the slabs are the host's).
 int quiesce(afe_engine *e) {
+  AFE_HIP(e, hipSetDevice(e->device));
+  if (e->p_failed) return refuse_failed(e);     // (host-visible arenas' getters come through here, not through main_stream)
   join_streams(e);
-  if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);     // (host-visible arenas' getters come through here)
   if (e->p_running) {
     volatile unsigned long long *st = p_status(e);
     const auto t0 = std::chrono::steady_clock::now();
     const bool deaf = afe_fault("sync_answer");      // (fault injection, dev-hooks builds: the host sees neither a park nor an answer)
     for (unsigned spins = 0;; spins++) {
       if (st[0] != 0 && !deaf) {                 // it has parked (idle host, or a stall): collect, finish what is left
-        int rc = persist_collect(e);
+        const int rc = persist_take_over(e);
         if (rc) return rc;
-        if (e->p_resume > e->p_next) { e->p_failed = true; return fail(e, AFE_ERR_HIP, "persistent step kernel ran past the authorised steps"); }
-        if (e->p_resume == e->p_next) break;
-        if ((rc = persist_launch(e))) return rc;
+        if (!e->p_running) break;
         continue;
       }
       if (e->p_sync_posted == e->p_next + 1) {
@@ -884,14 +902,12 @@ int quiesce(afe_engine *e) {
       }
       if ((spins & 0xfffu) == 0xfffu && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(afe_sync_patience_s())) {
         // Nothing answered and nothing parked: the grid is not going to.  The engine is marked failed (every later call says
-        // so at once instead of spinning another 20 s on the same posted request) and the request is withdrawn.
+        // so at once instead of spinning another 20 s on the same posted request) and the request is withdrawn (grid_failed).
         char msg[200];
         std::snprintf(msg, sizeof(msg), "persistent step kernel makes no progress (waiting for step %llu; request posted for %llu, answered %llu, pump at %llu)",
                       (unsigned long long)e->p_next, (unsigned long long)(e->p_sync_posted ? e->p_sync_posted - 1 : 0),
                       (unsigned long long)st[AFE_PERSIST_SYNC_WORD], (unsigned long long)st[1]);
-        e->p_failed = true;
-        e->p_sync_posted = 0;
-        return fail(e, AFE_ERR_HIP, msg);
+        return grid_failed(e, msg);
       }
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
@@ -904,9 +920,11 @@ int quiesce(afe_engine *e) {
   return AFE_OK;
 }
 
-long persist_refresh_steps() {
+// The grid now resident is old enough to retire (persist_step says why): persist_step ends it before the next step,
+// afe_sync instead of leaving it resident.
+bool persist_due_for_retirement(const afe_engine *e) {
   static const long refresh = [] { const char *s = afe_dev_env("AFE_PERSIST_REFRESH_STEPS"); return s && *s ? std::atol(s) : 512L; }();
-  return refresh;
+  return e->p_running && !e->p_prio && refresh > 0 && (long)(e->p_next - e->p_launch_start) >= refresh;
 }
 
 // The pump parks itself after 200 us without news.  If it decides to while entries are being written, they would wait
@@ -926,11 +944,7 @@ int persist_settle(afe_engine *e) {
     if (intent == 0 || intent - 1 >= e->p_next) return AFE_OK;    // not leaving, or leaving behind everything authorised
     if ((spins & 0xfffu) == 0xfffu && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) break;   // (collect below reports what is wrong)
   }
-  int rc = persist_collect(e);
-  if (rc) return rc;
-  if (e->p_resume > e->p_next) { e->p_failed = true; return fail(e, AFE_ERR_HIP, "persistent step kernel ran past the authorised steps"); }
-  if (e->p_resume < e->p_next) return persist_launch(e);
-  return AFE_OK;
+  return persist_take_over(e);
 }
 
 // Cache policy of the one-step launches (LaunchFlags::cache_policy).  Automatic: by what the Infinity Cache (256 MiB) can
@@ -968,13 +982,12 @@ int persist_step(afe_engine *e, uint64_t dt_us, int n_steps) {
   // finish their share early -- those with two chunks where others have three -- LEAVE at a park entry and stop competing,
   // while in a grid that stays they poll the ring until the slowest is done.  Where issue priority keeps the workers
   // together (persist_launch) there is nobody to send home and a grid lives on (131 072 / 262 144 vehicles, retired against
-  // not: 2.20 / 3.54 against 2.19 / 3.51).  Otherwise a grid that has served persist_refresh_steps() steps is retired here
-  // -- the host waits for what it has authorised, ~20 us of dispatch follow -- and at the next afe_sync (afe_sync below).
+  // not: 2.20 / 3.54 against 2.19 / 3.51).  Otherwise a grid that has served 512 steps (persist_due_for_retirement) is retired
+  // here -- the host waits for what it has authorised, ~20 us of dispatch follow -- and at the next afe_sync (afe_sync below).
   // AFE_PERSIST_REFRESH_STEPS=0: never.
-  if (e->p_running && !e->p_prio && persist_refresh_steps() > 0 && (long)(e->p_next - e->p_launch_start) >= persist_refresh_steps() && (rc = persist_park(e))) return rc;
-  if (e->p_running && st[0] != 0) {       // it parked itself (idle): collect it, a new grid starts below
-    if ((rc = persist_collect(e))) return rc;
-  }
+  if (persist_due_for_retirement(e) && (rc = persist_park(e))) return rc;
+  // it parked itself (idle): collected only, not taken over -- a new run may begin here, and the grid for what is waiting starts below, behind the new entries
+  if (e->p_running && st[0] != 0 && (rc = persist_collect(e))) return rc;
   if (!e->p_running && e->p_resume == e->p_next) {
     // nothing pending: a new run of equally long steps begins here.  Step index -> start time is linear from now on
     // (a resident grid derives the gust epoch of each of its steps from it, and so does persist_launch for a grid that
@@ -989,10 +1002,10 @@ int persist_step(afe_engine *e, uint64_t dt_us, int n_steps) {
     for (unsigned spins = 0;; spins++) {
       const uint64_t floor_ = e->p_running ? std::max<uint64_t>(st[1], e->p_resume) : e->p_resume;
       if (e->p_next - floor_ < AFE_PERSIST_HOST_RING - 128) break;
-      if (!e->p_running) {                // entries are waiting and nobody reads them
+      if (!e->p_running) {                // entries are waiting and nobody reads them (the grid collected above)
         if ((rc = persist_launch(e))) return rc;
       } else if (st[0] != 0) {
-        if ((rc = persist_collect(e))) return rc;
+        if ((rc = persist_take_over(e))) return rc;
       } else if (spins > 2000000000u) {
         return fail(e, AFE_ERR_HIP, "persistent step kernel makes no progress");
       }
@@ -1069,7 +1082,7 @@ static int create_engine(afe_engine **out, int64_t n_vehicles, int precision, in
     if ((err = hipHostGetDevicePointer(&e->arena, hp, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", err);
   } else if ((err = hipMalloc(&e->arena, bytes)) != hipSuccess) return bail("hipMalloc", err);
   e->arena_bytes = bytes;
-  if ((err = hipMemsetAsync(e->arena, 0, bytes, main_stream(e))) != hipSuccess) return bail("hipMemset", err);
+  if ((err = hipMemsetAsync(e->arena, 0, bytes, e->stream)) != hipSuccess) return bail("hipMemset", err);
   char *p = (char *)e->arena;
   auto carve = [&](size_t nbytes) { void *r = p; p += nbytes; return r; };
   e->pos = carve(3 * S * es);
@@ -1095,13 +1108,13 @@ static int create_engine(afe_engine **out, int64_t n_vehicles, int precision, in
       if (precision == AFE_F64) ((double *)ones.data())[k] = 1.0;
       else ((float *)ones.data())[k] = 1.0f;
     }
-    if ((err = hipMemcpyAsync(e->att, ones.data(), S * es, hipMemcpyHostToDevice, main_stream(e))) != hipSuccess)
+    if ((err = hipMemcpyAsync(e->att, ones.data(), S * es, hipMemcpyHostToDevice, e->stream)) != hipSuccess)
       return bail("hipMemcpy", err);
-    if ((err = hipStreamSynchronize(main_stream(e))) != hipSuccess) return bail("hipStreamSynchronize", err);
+    if ((err = hipStreamSynchronize(e->stream)) != hipSuccess) return bail("hipStreamSynchronize", err);
   }
-  if (launch_seed_rng(e->rng, e->n, e->first_global, e->seed_policy, main_stream(e)) != 0)
+  if (launch_seed_rng(e->rng, e->n, e->first_global, e->seed_policy, e->stream) != 0)
     return bail("seed kernel launch (is the gfx950 code object present?)", hipGetLastError());
-  if ((err = hipStreamSynchronize(main_stream(e))) != hipSuccess) return bail("seed kernel", err);
+  if ((err = hipStreamSynchronize(e->stream)) != hipSuccess) return bail("seed kernel", err);
   if (const char *fm = std::getenv("AFE_FORCE_STEP_MODE")) {   // test hook: every engine of this process steps by the resident grid where it can (1 persistent, 3 resident state)
     const int m = std::atoi(fm);
     if (m >= AFE_STEP_LAUNCH && m <= AFE_STEP_RESIDENT) e->step_mode = m;
@@ -1127,7 +1140,7 @@ extern "C" int afe_create_host_visible(afe_engine **out, int64_t n_vehicles, int
 extern "C" int afe_destroy(afe_engine *e) {
   if (!e) return AFE_ERR_INVALID_ARG;
   (void)hipSetDevice(e->device);
-  if (e->p_running) (void)persist_park(e);
+  if (e->p_running) (void)persist_park(e);     // (not through the gate: a failed engine's grid is still waited for, then freed or leaked)
   if (e->aql) {
     const bool left = afe::aql_close(e->aql);     // waits (30 s) for a grid that did not take the park
     e->aql = nullptr;
@@ -1164,8 +1177,9 @@ extern "C" const char *afe_last_error(const afe_engine *e) { return e ? e->err.c
 
 extern "C" int afe_set_stream(afe_engine *e, void *hip_stream) {
   if (!e) return AFE_ERR_INVALID_ARG;
-  AFE_HIP(e, hipSetDevice(e->device));
-  AFE_HIP(e, hipStreamSynchronize(main_stream(e)));   // (joins the side stream first)
+  const int rc = main_stream(e);                     // (joins the side stream first)
+  if (rc) return rc;
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
   e->stream = hip_stream ? (hipStream_t)hip_stream : e->own_stream;
   return AFE_OK;
 }
@@ -1225,7 +1239,6 @@ extern "C" int afe_set_vehicle_types(afe_engine *e, int64_t first, int64_t count
     if (type_index[k] >= e->table.size())
       return fail(e, AFE_ERR_INVALID_ARG, "type index " + std::to_string(type_index[k]) + " of vehicle " +
                                               std::to_string(first + k) + " is outside the type table");
-  AFE_HIP(e, hipSetDevice(e->device));
   if ((rc = copy_in(e, e->type, 1, 1, first, count, type_index))) return rc;
   if (e->type_host.size() != (size_t)e->n) e->type_host.assign((size_t)e->n, 0);
   std::memcpy(e->type_host.data() + first, type_index, (size_t)count);
@@ -1243,15 +1256,15 @@ extern "C" int afe_set_imu_noise(afe_engine *e, int enabled, double sigma_gyro, 
   if (!e || !(sigma_gyro >= 0) || !(sigma_acc >= 0) ||
       (seed_policy != AFE_SEED_REFERENCE && seed_policy != AFE_SEED_DECORRELATED && seed_policy != AFE_SEED_COUNTER))
     return fail(e, AFE_ERR_INVALID_ARG, "bad noise configuration");
-  { const int prc = persist_park(e); if (prc) return prc; }   // a resident grid carries the old configuration
+  const int rc = main_stream(e);             // a resident grid carries the old configuration
+  if (rc) return rc;
   e->noise = enabled != 0;
   e->sigma_gyro = sigma_gyro;
   e->sigma_acc = sigma_acc;
   if (seed_policy != e->seed_policy) {
     e->seed_policy = seed_policy;
-    AFE_HIP(e, hipSetDevice(e->device));
     // (the counter policy keeps no per-vehicle word; the slab stays what it was -- valid minstd_rand0 words)
-    if (seed_policy != AFE_SEED_COUNTER && launch_seed_rng(e->rng, e->n, e->first_global, seed_policy, main_stream(e)) != 0)
+    if (seed_policy != AFE_SEED_COUNTER && launch_seed_rng(e->rng, e->n, e->first_global, seed_policy, e->stream) != 0)
       return fail(e, AFE_ERR_HIP, "seed kernel launch failed");
   }
   return AFE_OK;
@@ -1282,14 +1295,12 @@ extern "C" int afe_set_rng_state(afe_engine *e, int64_t first, int64_t count, co
   if (!state) return fail(e, AFE_ERR_INVALID_ARG, "state is NULL");
   for (int64_t k = 0; k < count; k++)
     if (state[k] == 0 || state[k] >= 2147483647u) return fail(e, AFE_ERR_INVALID_ARG, "minstd_rand0 state must be in [1, 2^31-2]");
-  AFE_HIP(e, hipSetDevice(e->device));
   return copy_in(e, e->rng, 4, 1, first, count, state);
 }
 extern "C" int afe_get_rng_state(afe_engine *e, int64_t first, int64_t count, uint32_t *state) {
   int rc = check_range(e, first, count);
   if (rc) return rc;
   if (!state) return fail(e, AFE_ERR_INVALID_ARG, "state is NULL");
-  AFE_HIP(e, hipSetDevice(e->device));
   return copy_out(e, e->rng, 4, 1, first, count, state);
 }
 
@@ -1297,7 +1308,6 @@ extern "C" int afe_set_motor_cmds(afe_engine *e, int64_t first, int64_t count, c
   int rc = check_range(e, first, count);
   if (rc) return rc;
   if (!cmd4) return fail(e, AFE_ERR_INVALID_ARG, "cmd4 is NULL");
-  AFE_HIP(e, hipSetDevice(e->device));
   if ((rc = materialize_motor(e))) return rc;   // the speeds of the last step come from the OLD commands
   return copy_in(e, e->cmd, 4, 4, first, count, cmd4);
 }
@@ -1305,16 +1315,15 @@ extern "C" int afe_get_motor_cmds(afe_engine *e, int64_t first, int64_t count, f
   int rc = check_range(e, first, count);
   if (rc) return rc;
   if (!cmd4) return fail(e, AFE_ERR_INVALID_ARG, "cmd4 is NULL");
-  AFE_HIP(e, hipSetDevice(e->device));
   return copy_out(e, e->cmd, 4, 4, first, count, cmd4);
 }
 
 extern "C" int afe_set_rates_logic(afe_engine *e, const afe_rates_logic_params *table, int n_types) {
   if (!e) return AFE_ERR_INVALID_ARG;
-  AFE_HIP(e, hipSetDevice(e->device));
-  { const int mrc = materialize_motor(e); if (mrc) return mrc; }   // from here on the logic rewrites the commands
+  int grc = main_stream(e);
+  if (grc || (grc = materialize_motor(e))) return grc;   // from here on the logic rewrites the commands
   if (!table) {
-    AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
+    AFE_HIP(e, hipStreamSynchronize(e->stream));
     e->logic_on = false;
     return AFE_OK;
   }
@@ -1363,7 +1372,6 @@ extern "C" int afe_set_rates_commands(afe_engine *e, int64_t first, int64_t coun
   if (rc) return rc;
   if (!e->logic_on) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_rates_logic has not been called");
   if (!thrust_norm || !ang_vel3) return fail(e, AFE_ERR_INVALID_ARG, "command arrays are NULL");
-  AFE_HIP(e, hipSetDevice(e->device));
   if ((rc = copy_in(e, e->rates_cmd, 4, 1, first, count, thrust_norm))) return rc;
   if ((rc = copy_in(e, e->rates_cmd + e->stride, 4, 3, first, count, ang_vel3))) return rc;
   return fill_rows(e, e->have_cmd, 1, 1, first, count, 1);
@@ -1390,7 +1398,6 @@ extern "C" int afe_set_commands_from_radio(afe_engine *e, int64_t first, int64_t
                                               std::to_string(first + k) + " needs the host-side logic");
     }
   }
-  AFE_HIP(e, hipSetDevice(e->device));
   if ((rc = copy_in(e, e->rates_cmd, 4, 4, first, count, cmd.data()))) return rc;
   return copy_in(e, e->have_cmd, 1, 1, first, count, have.data());
 }
@@ -1404,20 +1411,31 @@ extern "C" int afe_set_external_torque(afe_engine *e, int64_t first, int64_t cou
   return set_wrench(e, e->ext_torque, e->has_ext_torque, first, count, torque3);
 }
 
+// one launch of afe_step's launch mode: `chunk` fused steps of vehicles [0, half) on the main stream and, split, of [half, n) on the side stream
+template <typename R>
+static int launch_chunk(afe_engine *e, const LaunchFlags &f, double dt, int chunk, unsigned long long mask, uint64_t tick_base, const DevLogic *ulogic, bool split, int64_t half) {
+  const DevParams<R> *uniform = e->types_uniform ? &host_table(e, R())[0] : nullptr;
+  StepView<R> v;
+  fill_view(e, v);
+  v.dt = (R)dt; v.inv_dt = (R)(1.0 / dt); v.n_steps = chunk; v.tick_mask = mask; v.tick_base = tick_base;
+  v.end = half;
+  const int lrc = launch_step(v, f, uniform, ulogic, e->stream);
+  if (!split || lrc != 0) return lrc;
+  v.first = half; v.end = e->n;
+  return launch_step(v, f, uniform, ulogic, e->side_stream);
+}
+
 extern "C" int afe_step(afe_engine *e, uint64_t dt_us, int n_steps) {
   if (!e || n_steps < 0) return fail(e, AFE_ERR_INVALID_ARG, "n_steps must be >= 0");
   if (e->table.empty()) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_type_table has not been called");
   if (n_steps == 0) return AFE_OK;
   const double dt = us_to_seconds(dt_us);  // Timer::GetSeconds<double>, Timer.hpp:36-38
   if (dt < 1e-6) return AFE_OK;            // Quadcopter_T.cpp:88-90
-  AFE_HIP(e, hipSetDevice(e->device));
+  AFE_HIP(e, hipSetDevice(e->device));     // (not through the gate: a resident grid stays and takes the steps)
+  if (e->p_failed) return refuse_failed(e);
   int rc = refresh_table(e, dt);
   if (rc) return rc;
   if (e->logic_on && (rc = refresh_logic(e))) return rc;
-  if (e->p_failed) {
-    if (e->p_fail_msg.empty()) e->p_fail_msg = e->err;      // the first refusal after the failure: err still holds its text
-    return fail(e, AFE_ERR_HIP, "a persistent step kernel failed earlier (" + e->p_fail_msg + "); create a new engine");
-  }
   // AFE_STEP_AUTO and a call that asks for several steps at once: nobody can look at the steps in between, so the fused
   // launch (state in registers from step to step, one load and one store per call) is the faster way to the same bits --
   // from 2 steps per call at 2^19 vehicles and more, from 8 at any size (measured: bench.py sweep, fused2 / fused50
@@ -1471,28 +1489,8 @@ extern "C" int afe_step(afe_engine *e, uint64_t dt_us, int n_steps) {
       AFE_HIP(e, hipStreamWaitEvent(e->side_stream, e->ev_main, 0));
       e->split_dirty = true;
     }
-    int lrc;
-    if (e->precision == AFE_F64) {
-      StepView<double> v;
-      fill_view(e, v);
-      v.dt = dt; v.inv_dt = 1.0 / dt; v.n_steps = chunk; v.tick_mask = mask; v.tick_base = tick_base;
-      v.end = half;
-      lrc = launch_step_f64(v, f, e->types_uniform ? &e->table_f64[0] : nullptr, ulogic, e->stream);
-      if (split && lrc == 0) {
-        v.first = half; v.end = e->n;
-        lrc = launch_step_f64(v, f, e->types_uniform ? &e->table_f64[0] : nullptr, ulogic, e->side_stream);
-      }
-    } else {
-      StepView<float> v;
-      fill_view(e, v);
-      v.dt = (float)dt; v.inv_dt = (float)(1.0 / dt); v.n_steps = chunk; v.tick_mask = mask; v.tick_base = tick_base;
-      v.end = half;
-      lrc = launch_step_f32(v, f, e->types_uniform ? &e->table_f32[0] : nullptr, ulogic, e->stream);
-      if (split && lrc == 0) {
-        v.first = half; v.end = e->n;
-        lrc = launch_step_f32(v, f, e->types_uniform ? &e->table_f32[0] : nullptr, ulogic, e->side_stream);
-      }
-    }
+    const int lrc = e->precision == AFE_F64 ? launch_chunk<double>(e, f, dt, chunk, mask, tick_base, ulogic, split, half)
+                                            : launch_chunk<float>(e, f, dt, chunk, mask, tick_base, ulogic, split, half);
     if (lrc != 0) return fail(e, AFE_ERR_HIP, std::string("step kernel launch: ") + hipGetErrorString((hipError_t)lrc));
     e->stream_pending = true;
     if (motor_lazy(e)) e->motor_stale = true;
@@ -1504,7 +1502,7 @@ extern "C" int afe_step(afe_engine *e, uint64_t dt_us, int n_steps) {
 
 extern "C" int afe_set_noise_seed(afe_engine *e, uint64_t seed) {
   if (!e) return AFE_ERR_INVALID_ARG;
-  const int rc = persist_park(e);
+  const int rc = main_stream(e);             // (a resident grid carries the old key)
   if (rc) return rc;
   e->noise_seed = seed;
   return AFE_OK;
@@ -1514,8 +1512,7 @@ extern "C" int afe_set_gust_process(afe_engine *e, int enabled, uint64_t seed, d
   if (!e) return AFE_ERR_INVALID_ARG;
   if (enabled && (!(sigma_max >= 0) || !std::isfinite(sigma_max) || period_us == 0 || (n_global > 0 && n_global < e->first_global + e->n)))
     return fail(e, AFE_ERR_INVALID_ARG, "gust process: sigma_max >= 0, period > 0, n_global >= first_global_index + n_vehicles (or 0: this ensemble alone)");
-  AFE_HIP(e, hipSetDevice(e->device));
-  const int rc = persist_park(e);
+  const int rc = main_stream(e);
   if (rc) return rc;
   e->gust_on = enabled != 0;
   e->gust_seed = seed;
@@ -1531,15 +1528,12 @@ extern "C" int afe_get_external_force(afe_engine *e, int64_t first, int64_t coun
   int rc = check_range(e, first, count);
   if (rc) return rc;
   if (!force3) return fail(e, AFE_ERR_INVALID_ARG, "force3 is NULL");
-  AFE_HIP(e, hipSetDevice(e->device));
-  if (e->precision == AFE_F64) return get_field<double>(e, e->ext_force, 3, first, count, force3);
-  return get_field<float>(e, e->ext_force, 3, first, count, force3);
+  return get_real(e, e->ext_force, 3, first, count, force3);
 }
 
 extern "C" int afe_set_step_mode(afe_engine *e, int mode) {
   if (!e || mode < AFE_STEP_LAUNCH || mode > AFE_STEP_RESIDENT) return fail(e, AFE_ERR_INVALID_ARG, "step mode: 0 (launches), 1 (persistent), 2 (automatic) or 3 (resident state)");
-  AFE_HIP(e, hipSetDevice(e->device));
-  const int rc = persist_park(e);
+  const int rc = main_stream(e);
   if (rc) return rc;
   e->step_mode = mode;
   return AFE_OK;
@@ -1547,14 +1541,14 @@ extern "C" int afe_set_step_mode(afe_engine *e, int mode) {
 
 extern "C" int afe_steps_completed(afe_engine *e, uint64_t *steps) {
   if (!e || !steps) return AFE_ERR_INVALID_ARG;
+  if (e->p_failed) return refuse_failed(e);
   uint64_t pending = 0;
   if (e->p_running && p_status(e)[0] != 0) {
     // the grid has parked itself (a quiet host): steps authorised around that moment wait for a new grid -- start it here,
     // or a host that only watches this word would watch for ever
     AFE_HIP(e, hipSetDevice(e->device));
-    int rc = persist_collect(e);
+    const int rc = persist_take_over(e);
     if (rc) return rc;
-    if (e->p_resume < e->p_next && (rc = persist_launch(e))) return rc;
   }
   if (e->p_running) {
     // (the pump's sweep over the workers' marks, or the workers' own answer to a sync request -- whichever is further)
@@ -1603,8 +1597,7 @@ extern "C" int afe_set_cache_policy(afe_engine *e, int policy) {
 
 extern "C" int afe_set_resident_queue(afe_engine *e, int mode) {
   if (!e || mode < -1 || mode > 1) return fail(e, AFE_ERR_INVALID_ARG, "resident queue: -1 (automatic), 0 (the HIP stream) or 1 (the engine's own queue)");
-  AFE_HIP(e, hipSetDevice(e->device));
-  const int rc = persist_park(e);
+  const int rc = main_stream(e);
   if (rc) return rc;
   e->aql_mode = mode;
   return AFE_OK;
@@ -1638,29 +1631,24 @@ extern "C" int afe_steps_until_tick(const afe_engine *e, uint64_t dt_us, int *n_
 
 extern "C" int afe_sync(afe_engine *e) {
   if (!e) return AFE_ERR_INVALID_ARG;
-  AFE_HIP(e, hipSetDevice(e->device));
-  if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);     // a grid that gave up, did not come back or never answered: said at once, nothing is waited for again
-  if (e->p_running && e->p_on_aql && !e->view_exported &&
-      !(!e->p_prio && persist_refresh_steps() > 0 && (long)(e->p_next - e->p_launch_start) >= persist_refresh_steps())) {     // (an aged grid is retired: persist_step)
+  // (a grid that gave up, did not come back or never answered: quiesce and main_stream both say so at once, nothing is waited for again)
+  if (e->p_running && e->p_on_aql && !e->view_exported && !persist_due_for_retirement(e)) {     // (an aged grid is retired: persist_step)
     // Every authorised step has run and its stores are acknowledged; the grid STAYS (it lives on the engine's own queue,
     // which no HIP synchronisation waits for) and takes the next afe_step without a launch.  Whoever reads the state does
     // so through an entry point of the engine, which ends the grid first (kernel end = the caches written back).  Once
     // afe_get_device_view has handed the slabs out, afe_sync ends the grid as it always did: a reader the engine does
     // not know about must find them in memory.
-    const int rc = quiesce(e);
-    if (rc) return rc;
-    if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);
-    return AFE_OK;
+    return quiesce(e);
   }
-  AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
-  if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);
+  const int rc = main_stream(e);
+  if (rc) return rc;
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
   return AFE_OK;
 }
 
 extern "C" int afe_grid_time(afe_engine *e, uint64_t *device_ns, uint64_t *steps) {
   if (!e || !device_ns || !steps) return AFE_ERR_INVALID_ARG;
-  AFE_HIP(e, hipSetDevice(e->device));
-  const int rc = persist_park(e);      // the grid now resident is counted too
+  const int rc = main_stream(e);       // the grid now resident is counted too
   if (rc) return rc;
   *device_ns = e->p_grid_ns;
   *steps = e->p_grid_steps;
@@ -1682,15 +1670,16 @@ extern "C" int afe_logic_ticks(const afe_engine *e, uint64_t *n_ticks) {
 extern "C" int afe_get_imu(afe_engine *e, int64_t first, int64_t count, float *gyro3, float *acc3) {
   int rc = check_range(e, first, count);
   if (rc) return rc;
-  AFE_HIP(e, hipSetDevice(e->device));
   if ((rc = copy_out(e, e->gyro, 4, 3, first, count, gyro3))) return rc;
   return copy_out(e, e->acc, 4, 3, first, count, acc3);
 }
 
 namespace afe {
-// for the other translation units of the library (afe_render.hip)
+// for the other translation units of the library (afe_render.hip).  Passes the gate but cannot report it: its users (camera,
+// clearance, gather, ranging) fetch the device view or pack the positions next to it, and THOSE calls carry the refusal.
 void engine_stream_device(afe_engine *e, void **stream, int *device) {
-  *stream = (void *)main_stream(e);
+  (void)main_stream(e);
+  *stream = (void *)e->stream;
   *device = e->device;
 }
 void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n) {
@@ -1701,13 +1690,12 @@ void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n) {
 // rewrite them on the main stream is ordered behind it (a device-side wait; in steady state the query issued a cycle
 // ago is long done and this costs nothing).
 void engine_query_join(afe_engine *e) {
-  if (!e->query_pending) return;
-  (void)hipStreamWaitEvent(main_stream(e), e->ev_q_done, 0);
+  if (!e->query_pending || main_stream(e) != AFE_OK) return;   // (refused: the caller's own pass through the gate says so)
+  (void)hipStreamWaitEvent(e->stream, e->ev_q_done, 0);
   e->query_pending = false;
 }
 // this shard's positions as planar fp32 [3][n] in the engine's own scratch, on its stream
 int engine_pack_to_scratch(afe_engine *e, float **scratch) {
-  engine_query_join(e);
   AFE_HIP(e, hipSetDevice(e->device));
   if (!e->pack_scratch) AFE_HIP(e, hipMalloc((void **)&e->pack_scratch, (size_t)e->n * 3 * sizeof(float)));
   const int rc = afe_pack_positions(e, e->pack_scratch);
@@ -1728,9 +1716,8 @@ static int device_view(afe_engine *e, afe_device_view *out, bool exported) {
   const size_t have = out->struct_bytes;
   if (have < offsetof(afe_device_view, pos_anchor_xy))
     return fail(e, AFE_ERR_INVALID_ARG, "afe_device_view::struct_bytes must be set to sizeof(afe_device_view) before the call (ABI version 2)");
-  AFE_HIP(e, hipSetDevice(e->device));
-  (void)main_stream(e);            // a resident grid ends here (its last stores are the caller's to read); split streams are joined
-  if (e->p_failed) return fail(e, AFE_ERR_HIP, e->err);
+  const int grc = main_stream(e);  // a resident grid ends here (its last stores are the caller's to read); split streams are joined
+  if (grc) return grc;
   if (exported) e->view_exported = true;   // from now on afe_sync leaves the slabs readable (it ends a resident grid)
   { const int mrc = materialize_motor(e); if (mrc) return mrc; }   // motor_speed is current as of this call
   afe_device_view v;
@@ -1826,7 +1813,7 @@ extern "C" int afe_event_destroy(void *event) {
 extern "C" int afe_event_record(afe_engine *e, void *event) {
   if (!e || !event) return AFE_ERR_INVALID_ARG;
   AFE_HIP(e, hipSetDevice(e->device));
-  if (e->p_running && !e->p_on_aql && !e->split_dirty && p_status(e)[0] == 0) {     // (a grid that has already left by itself takes the ordinary way)
+  if (!e->p_failed && e->p_running && !e->p_on_aql && !e->split_dirty && p_status(e)[0] == 0) {     // (a grid that has already left by itself takes the ordinary way)
     // A resident grid on the engine's stream: the event goes onto the stream BEHIND it and the grid is told to leave after
     // the last authorised step -- the event's time is then the moment the grid left the device, not the moment the host had
     // noticed (which is what recording after the park gave: ~10 us later, 0.5 us per step of a 20-step block).
@@ -1835,7 +1822,9 @@ extern "C" int afe_event_record(afe_engine *e, void *event) {
     e->stream_pending = true;
     return persist_park(e);
   }
-  AFE_HIP(e, hipEventRecord((hipEvent_t)event, main_stream(e)));
+  const int rc = main_stream(e);
+  if (rc) return rc;
+  AFE_HIP(e, hipEventRecord((hipEvent_t)event, e->stream));
   return AFE_OK;
 }
 extern "C" int afe_event_elapsed_ms(void *start, void *stop, float *ms) {
@@ -1904,9 +1893,9 @@ extern "C" int afe_save_checkpoint(afe_engine *e, void *host_buffer, uint64_t by
   uint64_t need = 0;
   if (!e || !host_buffer || afe_checkpoint_size(e, &need) != AFE_OK) return AFE_ERR_INVALID_ARG;
   if (bytes < need) return fail(e, AFE_ERR_INVALID_ARG, "checkpoint buffer too small");
-  AFE_HIP(e, hipSetDevice(e->device));
-  { const int mrc = materialize_motor(e); if (mrc) return mrc; }
-  AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
+  int rc = main_stream(e);
+  if (rc || (rc = materialize_motor(e))) return rc;
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
   CheckpointHeader h = {};
   h.magic = kCheckpointMagic; h.n = (uint64_t)e->n; h.stride = (uint64_t)e->stride; h.precision = (uint64_t)e->precision;
   h.arena_bytes = (uint64_t)e->arena_bytes; h.logic_bytes = e->logic_on ? (uint64_t)logic_arena_bytes(e) : 0;
@@ -1965,8 +1954,9 @@ extern "C" int afe_load_checkpoint(afe_engine *e, const void *host_buffer, uint6
         return fail(e, AFE_ERR_INVALID_ARG, "checkpoint holds an engine word outside [1, 2^31-2] (vehicle " + std::to_string(k) + ")");
     }
   }
-  AFE_HIP(e, hipSetDevice(e->device));
-  AFE_HIP(e, hipStreamSynchronize(main_stream(e)));
+  const int rc = main_stream(e);
+  if (rc) return rc;
+  AFE_HIP(e, hipStreamSynchronize(e->stream));
   // from here on the arena is being overwritten: whatever happens, nothing derived from the old one may survive
   e->table_dirty = true;
   e->logic_table_period = -1.0f;
@@ -2006,17 +1996,17 @@ int selftest_normals_any(afe_engine *e, const uint32_t *seeds, int64_t n, void *
   if (!e || !seeds || n <= 0 || !normals6 || !state_after) return fail(e, AFE_ERR_INVALID_ARG, "bad selftest arguments");
   for (int64_t k = 0; k < n; k++)
     if (seeds[k] == 0 || seeds[k] >= 2147483647u) return fail(e, AFE_ERR_INVALID_ARG, "minstd_rand0 state must be in [1, 2^31-2]");
-  AFE_HIP(e, hipSetDevice(e->device));
+  int rc = main_stream(e);
+  if (rc) return rc;
   uint32_t *d_seed = nullptr, *d_state = nullptr;
   void *d_out = nullptr;
   AFE_HIP(e, hipMalloc((void **)&d_seed, (size_t)n * 4));
   AFE_HIP(e, hipMalloc((void **)&d_state, (size_t)n * 4));
   AFE_HIP(e, hipMalloc((void **)&d_out, (size_t)n * 6 * elem_bytes));
-  int rc = AFE_OK;
   if (hipMemcpy(d_seed, seeds, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      (elem_bytes == 8 ? launch_normals_selftest(d_seed, n, (double *)d_out, d_state, main_stream(e))
-                       : launch_normals_selftest_f32(d_seed, n, (float *)d_out, d_state, main_stream(e))) != 0 ||
-      hipStreamSynchronize(main_stream(e)) != hipSuccess ||
+      (elem_bytes == 8 ? launch_normals_selftest(d_seed, n, (double *)d_out, d_state, e->stream)
+                       : launch_normals_selftest_f32(d_seed, n, (float *)d_out, d_state, e->stream)) != 0 ||
+      hipStreamSynchronize(e->stream) != hipSuccess ||
       hipMemcpy(normals6, d_out, (size_t)n * 6 * elem_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(state_after, d_state, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
     rc = fail(e, AFE_ERR_HIP, "normals selftest failed");
@@ -2034,11 +2024,12 @@ extern "C" int afe_selftest_normals_f32(afe_engine *e, const uint32_t *seeds, in
 
 extern "C" int afe_pack_positions(afe_engine *e, float *device_xyz) {
   if (!e || !device_xyz) return fail(e, AFE_ERR_INVALID_ARG, "device_xyz is NULL");
-  AFE_HIP(e, hipSetDevice(e->device));
+  int rc = main_stream(e);
+  if (rc) return rc;
   engine_query_join(e);
-  int rc = (e->precision == AFE_F64)
-               ? launch_pack_positions_f64((const double *)e->pos, e->anchor, e->stride, e->n, device_xyz, main_stream(e))
-               : launch_pack_positions_f32((const float *)e->pos, e->anchor, e->stride, e->n, device_xyz, main_stream(e));
+  rc = (e->precision == AFE_F64)
+           ? launch_pack_positions_f64((const double *)e->pos, e->anchor, e->stride, e->n, device_xyz, e->stream)
+           : launch_pack_positions_f32((const float *)e->pos, e->anchor, e->stride, e->n, device_xyz, e->stream);
   if (rc) return fail(e, AFE_ERR_HIP, "pack kernel launch failed");
   return AFE_OK;
 }
@@ -2054,10 +2045,11 @@ extern "C" int afe_nearest_neighbour_grid(afe_engine *e, const float *all_xyz, i
     return fail(e, AFE_ERR_INVALID_ARG, "bad nearest-neighbour arguments");
   if (e->first_global + e->n > n_all)
     return fail(e, AFE_ERR_OUT_OF_RANGE, "the gathered ensemble is smaller than this shard's global range");
-  AFE_HIP(e, hipSetDevice(e->device));
+  const int grc = main_stream(e);
+  if (grc) return grc;
   if (!e->world) { const int rc = world_create(e->device, &e->world); if (rc) return fail(e, rc, "shared-world scratch"); }
   engine_query_join(e);
-  const int rc = world_nearest(e->world, (void *)main_stream(e), all_xyz, n_all, e->first_global, e->n, cell_size, dist2_out, index_out);
+  const int rc = world_nearest(e->world, (void *)e->stream, all_xyz, n_all, e->first_global, e->n, cell_size, dist2_out, index_out);
   if (rc) return fail(e, rc, world_last_error(e->world));
   return AFE_OK;
 }
@@ -2068,7 +2060,8 @@ extern "C" int afe_nearest_neighbour_grid(afe_engine *e, const float *all_xyz, i
 extern "C" int afe_nearest_neighbour_async(afe_engine *e, const float *all_xyz, int64_t n_all, float *dist2_out, int32_t *index_out) {
   if (!e || !all_xyz || n_all <= 0 || !dist2_out || !index_out) return fail(e, AFE_ERR_INVALID_ARG, "bad nearest-neighbour arguments");
   if (e->first_global + e->n > n_all) return fail(e, AFE_ERR_OUT_OF_RANGE, "the gathered ensemble is smaller than this shard's global range");
-  AFE_HIP(e, hipSetDevice(e->device));
+  const int grc = main_stream(e);
+  if (grc) return grc;
   if (!e->world) { const int rc = world_create(e->device, &e->world); if (rc) return fail(e, rc, "shared-world scratch"); }
   if (!e->query_stream) {
     AFE_HIP(e, hipStreamCreateWithFlags(&e->query_stream, hipStreamNonBlocking));
@@ -2076,7 +2069,7 @@ extern "C" int afe_nearest_neighbour_async(afe_engine *e, const float *all_xyz, 
     AFE_HIP(e, hipEventCreateWithFlags(&e->ev_q_done, hipEventDisableTiming));
   }
   e->query_pending = false;      // a query already on the query stream is ordered before this one by the stream itself
-  AFE_HIP(e, hipEventRecord(e->ev_q_start, main_stream(e)));
+  AFE_HIP(e, hipEventRecord(e->ev_q_start, e->stream));
   AFE_HIP(e, hipStreamWaitEvent(e->query_stream, e->ev_q_start, 0));
   const int rc = world_nearest(e->world, (void *)e->query_stream, all_xyz, n_all, e->first_global, e->n, 0.0f, dist2_out, index_out);
   if (rc) return fail(e, rc, world_last_error(e->world));
@@ -2116,10 +2109,11 @@ extern "C" int afe_nearest_neighbour_bruteforce(afe_engine *e, const float *all_
                                                 int64_t n_queries, float *dist2_out, int32_t *index_out) {
   if (!e || !all_xyz || n_all <= 0 || !dev_queries || n_queries <= 0 || !dist2_out || !index_out)
     return fail(e, AFE_ERR_INVALID_ARG, "bad nearest-neighbour arguments");
-  AFE_HIP(e, hipSetDevice(e->device));
+  const int grc = main_stream(e);
+  if (grc) return grc;
   if (!e->world) { const int rc = world_create(e->device, &e->world); if (rc) return fail(e, rc, "shared-world scratch"); }
   engine_query_join(e);
-  const int rc = world_nearest_bruteforce(e->world, (void *)main_stream(e), all_xyz, n_all, e->first_global, dev_queries, n_queries,
+  const int rc = world_nearest_bruteforce(e->world, (void *)e->stream, all_xyz, n_all, e->first_global, dev_queries, n_queries,
                                           dist2_out, index_out);
   if (rc) return fail(e, rc, world_last_error(e->world));
   return AFE_OK;
