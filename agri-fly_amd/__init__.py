@@ -25,6 +25,9 @@ from .engine import (  # noqa: F401
     Camera,
     ClearanceMap,
     ContactMonitor,
+    GROUP_STATS_DTYPE,
+    GroupStats,
+    StatsMonitor,
     Comm,
     DeviceBuffer,
     DeviceView,
@@ -58,6 +61,7 @@ from .engine import (  # noqa: F401
     radio_decode,
     rates_logic_params_from_type,
     scene_check_hierarchy,
+    stats_check_layout,
     stream_probe,
     type_from_id,
 )

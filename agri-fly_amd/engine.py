@@ -53,6 +53,8 @@ ABI_FUNCTIONS = [
     "afe_clearance_query", "afe_clearance_query_stats", "afe_clearance_query_engine",
     "afe_contact_monitor_create", "afe_contact_monitor_update", "afe_contact_monitor_get", "afe_contact_monitor_reset",
     "afe_contact_monitor_destroy",
+    "afe_stats_check_layout", "afe_stats_create", "afe_stats_destroy", "afe_stats_info", "afe_stats_set_reference",
+    "afe_stats_set_histogram", "afe_stats_update", "afe_stats_get", "afe_stats_reset",
 ]
 
 
@@ -378,6 +380,15 @@ def library():
         "afe_contact_monitor_get": [vp, i64, i64, vp, vp, vp],
         "afe_contact_monitor_reset": [vp, i64, i64],
         "afe_contact_monitor_destroy": [vp],
+        "afe_stats_check_layout": [vp, ci, i64, C.POINTER(i64), C.POINTER(ci)],
+        "afe_stats_create": [eng, vp, ci, C.POINTER(vp)],
+        "afe_stats_destroy": [vp],
+        "afe_stats_info": [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(ci), C.POINTER(u64)],
+        "afe_stats_set_reference": [vp, i64, i64, vp],
+        "afe_stats_set_histogram": [vp, vp, ci],
+        "afe_stats_update": [vp, vp, vp],
+        "afe_stats_get": [vp, i64, i64, vp, vp, vp, vp, vp, vp],
+        "afe_stats_reset": [vp, i64, i64],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -754,6 +765,95 @@ class ContactMonitor:
     def close(self):
         if getattr(self, "_h", None):
             library().afe_contact_monitor_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GroupStats(C.Structure):
+    """afe_group_stats: one record per group of a StatsMonitor update (8-byte members only)."""
+    _fields_ = ([(k, C.c_int64) for k in ("count", "n_invalid", "n_grounded", "n_ever_invalid", "n_ever_grounded", "sum_n_valid",
+                                          "argmax_h2", "argmax_peak_h2")] +
+                [(k, C.c_double) for k in ("sum_h2", "sum_dz", "sum_dz2", "sum_v2", "sum_w2", "max_h2", "min_dz", "max_dz", "max_v2",
+                                           "max_w2", "min_up", "sum_peak_h2", "sum_acc_h2", "max_peak_h2", "min_min_up")])
+
+
+GROUP_STATS_DTYPE = np.dtype([(k, np.int64 if t is C.c_int64 else np.float64) for k, t in GroupStats._fields_])
+
+
+def stats_check_layout(edges, n_vehicles):
+    """Host-only: (n_chunks, levels) of the statistics layout for group edges over n_vehicles, after validating them."""
+    ed = np.ascontiguousarray(edges, dtype=np.int64)
+    nc, lv = C.c_int64(), C.c_int()
+    _status(library().afe_stats_check_layout(ed.ctypes.data, ed.size - 1, int(n_vehicles), C.byref(nc), C.byref(lv)))
+    return nc.value, lv.value
+
+
+class StatsMonitor:
+    """afe_stats_monitor: per-group statistics of the ensemble's state and per-vehicle latches, computed and kept on
+    the device (see the header).  Groups are [edges[g], edges[g+1]).  Borrows the ensemble: close it first."""
+
+    NEVER = np.uint64(0xffffffffffffffff)
+
+    def __init__(self, ensemble, edges):
+        ed = np.ascontiguousarray(edges, dtype=np.int64)
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self.n_groups = ed.size - 1
+        self.n_hist_edges = 0
+        self._keep = ensemble
+        _status(library().afe_stats_create(ensemble.handle, ed.ctypes.data, self.n_groups, C.byref(self._h)))
+
+    def mark(self, first=0, count=None):
+        """reference of vehicles [first, first+count) = where they are now (formed on the device)"""
+        count = self.n - first if count is None else count
+        _status(library().afe_stats_set_reference(self._h, int(first), int(count), None))
+
+    def set_reference(self, pos3, first=0):
+        """explicit reference points, planar [3, count], for vehicles [first, first+count)"""
+        p = np.ascontiguousarray(pos3, dtype=np.float64)
+        assert p.ndim == 2 and p.shape[0] == 3
+        _status(library().afe_stats_set_reference(self._h, int(first), p.shape[1], p.ctypes.data))
+
+    def set_histogram(self, edges_m=None):
+        """ascending edges in metres for the histogram of the horizontal deviation; None or empty: off"""
+        ed = np.ascontiguousarray([] if edges_m is None else edges_m, dtype=np.float64).ravel()
+        _status(library().afe_stats_set_histogram(self._h, ed.ctypes.data if ed.size else None, ed.size))
+        self.n_hist_edges = ed.size
+
+    def update(self):
+        """-> (records: structured array [n_groups] of GROUP_STATS_DTYPE, histogram int64 [n_groups, n_edges+1] or None)"""
+        rec = np.empty(self.n_groups, GROUP_STATS_DTYPE)
+        hist = np.empty((self.n_groups, self.n_hist_edges + 1), np.int64) if self.n_hist_edges else None
+        _status(library().afe_stats_update(self._h, rec.ctypes.data, None if hist is None else hist.ctypes.data))
+        return rec, hist
+
+    def latches(self, first=0, count=None):
+        """-> dict(peak_h2, min_up, acc_h2 [count] float64, n_valid [count] int64, first_grounded_us, first_invalid_us
+        [count] uint64 (NEVER: none))"""
+        count = self.n - first if count is None else count
+        out = dict(peak_h2=np.empty(count), min_up=np.empty(count), acc_h2=np.empty(count), n_valid=np.empty(count, np.int64),
+                   first_grounded_us=np.empty(count, np.uint64), first_invalid_us=np.empty(count, np.uint64))
+        _status(library().afe_stats_get(self._h, int(first), int(count), *[a.ctypes.data for a in out.values()]))
+        return out
+
+    def reset(self, first=0, count=None):
+        count = self.n - first if count is None else count
+        _status(library().afe_stats_reset(self._h, int(first), int(count)))
+
+    def info(self):
+        ng, nv, ne, nu = C.c_int(), C.c_int64(), C.c_int(), C.c_uint64()
+        _status(library().afe_stats_info(self._h, C.byref(ng), C.byref(nv), C.byref(ne), C.byref(nu)))
+        return {"n_groups": ng.value, "n_vehicles": nv.value, "n_hist_edges": ne.value, "n_updates": nu.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_stats_destroy(self._h)
             self._h = C.c_void_p()
             self._keep = None
 

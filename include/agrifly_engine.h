@@ -490,6 +490,65 @@ int afe_contact_monitor_get(afe_contact_monitor *c, int64_t first, int64_t count
 int afe_contact_monitor_reset(afe_contact_monitor *c, int64_t first, int64_t count);
 int afe_contact_monitor_destroy(afe_contact_monitor *c);   /* NULL is AFE_ERR_INVALID_ARG */
 
+/* ---- ensemble statistics ---------------------------------------------------
+ * What a Monte-Carlo sweep ends with: the distribution of the ensemble's state
+ * per parameter bin, now and over the flight, without downloading the state.
+ * A statistics monitor reads the engine's slabs on the device (it never writes
+ * one), keeps per-vehicle latches resident and returns one record per GROUP of
+ * vehicles.  Groups are contiguous index ranges given by n_groups + 1
+ * non-decreasing edges, 0 <= edges[0], edges[n_groups] <= n_vehicles; group g is
+ * [edges[g], edges[g+1]); 1 <= n_groups <= 65536; empty groups are allowed and
+ * vehicles outside every group are never read or written.
+ * Every value is specified operation by operation in csrc/afe_stats.hip (IEEE
+ * double, + - * and comparisons only; sums in a fixed tree, so no result
+ * depends on grid shape or scheduling).  Per vehicle, against its reference
+ * point (rx, ry, rz):  dx = X - rx, dy = Y - ry, dz = Z - rz with X, Y, Z as
+ * afe_get_state forms them;  h2 = dx*dx + dy*dy;  v2 and w2 the squared speed
+ * and body rate;  up = R[8] of the attitude (cosine of the tilt);  valid = the
+ * 13 state values and dx, dy, dz are finite;  grounded = valid and Z <= 0.
+ * Indices are engine-local.  Not covered: merging records across shards. */
+typedef struct afe_stats_monitor afe_stats_monitor;
+typedef struct afe_group_stats {          /* 8-byte members only; the layout is ABI */
+  int64_t count, n_invalid, n_grounded;            /* now; count = edges[g+1] - edges[g] */
+  int64_t n_ever_invalid, n_ever_grounded;         /* latches */
+  int64_t sum_n_valid;                             /* over the group, of the per-vehicle update counts */
+  int64_t argmax_h2, argmax_peak_h2;               /* lowest index among equal values; -1 with no candidate */
+  double sum_h2, sum_dz, sum_dz2, sum_v2, sum_w2;  /* tree sums over the valid vehicles, now */
+  double max_h2, min_dz, max_dz, max_v2, max_w2, min_up;   /* over the valid vehicles, now; -inf / +inf with none */
+  double sum_peak_h2, sum_acc_h2;                  /* tree sums over every vehicle's latch */
+  double max_peak_h2, min_min_up;                  /* over every vehicle's latch */
+} afe_group_stats;
+
+/* Pure host (no GPU): validates the edges against n_vehicles; n_chunks = sum over groups of ceil(size / 256),
+ * levels = depth of the deepest group's summation tree (ceil(log2(size)); 0 for sizes 0 and 1).  NULL edges, n_groups
+ * outside 1..65536, a negative or decreasing edge: AFE_ERR_INVALID_ARG; an edge beyond n_vehicles:
+ * AFE_ERR_OUT_OF_RANGE.  The outputs may be NULL. */
+int afe_stats_check_layout(const int64_t *edges, int n_groups, int64_t n_vehicles, int64_t *n_chunks, int *levels);
+
+/* Latches initial, reference = where each vehicle is now.  The monitor BORROWS the engine: destroy it first. */
+int afe_stats_create(afe_engine *e, const int64_t *edges, int n_groups, afe_stats_monitor **out);
+int afe_stats_destroy(afe_stats_monitor *m);   /* NULL is AFE_ERR_INVALID_ARG */
+int afe_stats_info(const afe_stats_monitor *m, int *n_groups, int64_t *n_vehicles, int *n_hist_edges, uint64_t *n_updates);
+/* Reference points of vehicles [first, first+count): pos3 planar [3][count], finite (else AFE_ERR_INVALID_ARG);
+ * NULL: mark where they are now, on the device.  count == 0 with a valid range is AFE_OK without touching the engine. */
+int afe_stats_set_reference(afe_stats_monitor *m, int64_t first, int64_t count, const double *pos3);
+/* Histogram of the horizontal deviation per group: up to 63 ascending finite edges > 0 in metres (else
+ * AFE_ERR_INVALID_ARG); a valid vehicle falls into bin #{k : edges_m[k]^2 <= h2}.  n_edges == 0 (edges_m may be NULL): off. */
+int afe_stats_set_histogram(afe_stats_monitor *m, const double *edges_m, int n_edges);
+/* One pass over the grouped vehicles at the engine's current state and time (afe_time_us), on the engine's stream (a
+ * resident step grid ends first): updates the latches and writes n_groups records to groups_out and, if hist_out is
+ * not NULL, int64 counts [n_groups][n_edges + 1] (hist_out without a histogram is AFE_ERR_INVALID_ARG).  Nothing is
+ * allocated; the records and the histogram are the only bytes that cross the bus, in one copy. */
+int afe_stats_update(afe_stats_monitor *m, afe_group_stats *groups_out, int64_t *hist_out);
+/* The latches of vehicles [first, first+count) (any output may be NULL): peak_h2 = largest h2 seen (initially 0),
+ * min_up = smallest up seen (+inf), acc_h2 = sum of h2 over the updates (0), n_valid = updates in which the vehicle was
+ * valid, first_grounded_us / first_invalid_us = afe_time_us of the first update that found it grounded / not valid
+ * (UINT64_MAX: never). */
+int afe_stats_get(afe_stats_monitor *m, int64_t first, int64_t count, double *peak_h2, double *min_up, double *acc_h2,
+                  int64_t *n_valid, uint64_t *first_grounded_us, uint64_t *first_invalid_us);
+/* latches of vehicles [first, first+count) back to initial; the reference stays */
+int afe_stats_reset(afe_stats_monitor *m, int64_t first, int64_t count);
+
 /* Device scratch helpers for hosts without their own HIP allocator (ctypes). */
 int afe_device_alloc(int device, uint64_t bytes, void **out);
 int afe_device_free(void *p);
