@@ -16,6 +16,7 @@
 // instantiation rounds identically: the fp64 build tracks the CPU oracle to
 // ~1e-15 and the fp32 build differs from it only by fp32 rounding.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "afe_device.h"
@@ -62,6 +63,12 @@ __device__ __forceinline__ void mat_vec(const M *A, R x, R y, R z, R &ox, R &oy,
 }
 
 // ---------------------------------------------------------------------------
+#ifndef AFE_KERNARG_RELOAD
+#define AFE_KERNARG_RELOAD 1   // 0: the headline instantiation of the resident grid keeps its kernel arguments in registers across its loops like the others, kept for A/B timing
+#endif
+#ifndef AFE_EXACT_TRIMS
+#define AFE_EXACT_TRIMS 1      // 0: the accepted candidates evaluated with libstdc++'s operations one for one (2 c - 1 in two roundings, the canonical value clamped below 1), kept for A/B timing
+#endif
 #ifndef AFE_ACCEPT_LOOP
 #define AFE_ACCEPT_LOOP 2   // 1: the first form of the acceptance loop (selects on a slot number), kept for A/B timing
 #endif
@@ -100,7 +107,14 @@ __device__ __forceinline__ double canonical53(uint32_t &s) {
   const double q0 = sum * y;
   const double r = __builtin_fma(-q0, b, sum);
   double ret = __builtin_fma(r, y, q0);
+  // libstdc++ clamps here: if (ret >= 1.0) ret = nextafter(1, 0).  With THIS engine the clamp is dead code: the correctly
+  // rounded quotient reaches 1.0 only for a high word of 2147483646 (any smaller one leaves it at most 1 - 4.6e-10) AND a
+  // low word within 256 of the top, but the high word is 16807 times the low word mod 2^31 - 1, so a high word of 2147483646
+  // (== -1) fixes the low one at 2^31 - 1 - 16807^-1 = 739806647 and the quotient at 1 - 3.05e-10.  Left out (a compare and two
+  // selects per call, 18 vector instructions per tick); AFE_EXACT_TRIMS=0 puts it back.  tests/test_gpu_noise_loop.py holds the argument.
+#if !AFE_EXACT_TRIMS
   if (ret >= 1.0) ret = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
+#endif
   return ret;
 }
 
@@ -178,8 +192,15 @@ __device__ __forceinline__ float polar_multiplier_f32(double r2) {
 // with libstdc++'s roundings (bits/random.tcc normal_distribution::operator()).
 __device__ __forceinline__ void polar_candidate(uint32_t &s, double &x, double &y, double &r2) {
 #pragma clang fp contract(off)
+  // 2 c - 1 as ONE fma: 2 c is exact (c < 1, a power-of-two factor), so the fma rounds the same real number that
+  // libstdc++'s separately rounded product and difference do -- the same double, one fp64 instruction less per coordinate
+#if AFE_EXACT_TRIMS
+  x = __builtin_fma(2.0, canonical53(s), -1.0);
+  y = __builtin_fma(2.0, canonical53(s), -1.0);
+#else
   x = 2.0 * canonical53(s) - 1.0;
   y = 2.0 * canonical53(s) - 1.0;
+#endif
   r2 = x * x + y * y;
 }
 
@@ -206,8 +227,13 @@ __device__ __forceinline__ void three_accepted(uint32_t &s, uint32_t &st0, uint3
   // bit pattern (r2~ >= 0: bit patterns order like the values); "too close to call" is one more; and the three
   // words are kept as a shift register that accepted lanes push into under the execution mask (three moves)
   // instead of three compare + select pairs on a slot number.
+  // The bookkeeping lives in wave masks, i.e. in scalar registers and scalar instructions: the two compares ARE the
+  // ballots (a compare under a partial execution mask writes zeros for the lanes that have left, so nothing is masked
+  // again); m1 / m2 / m3 hold the lanes with at least one / two / three accepted candidates, which replaces a
+  // per-lane count, its increment and its compare; and the push, the rare branch and the exit take their lane
+  // sets straight from those masks.
   st0 = s; st1 = s; st2 = s;   // after the loop: the engine word before the 1st / 2nd / 3rd accepted candidate
-  int got = 0;
+  uint64_t m1 = 0, m2 = 0, m3 = 0;
   const uint32_t kLo = __builtin_bit_cast(uint32_t, 1e-5f), kUp = __builtin_bit_cast(uint32_t, 1.0f - 1e-5f),
                  kTop = __builtin_bit_cast(uint32_t, 1.0f + 1e-5f);
   for (;;) {
@@ -219,22 +245,24 @@ __device__ __forceinline__ void three_accepted(uint32_t &s, uint32_t &st0, uint3
     const float xf = __builtin_fmaf((float)(hx - 1u), 2.0f * kInvR, -1.0f);
     const float yf = __builtin_fmaf((float)(hy - 1u), 2.0f * kInvR, -1.0f);
     const uint32_t rb = __builtin_bit_cast(uint32_t, __builtin_fmaf(xf, xf, yf * yf));
-    bool accept = (rb - (kLo + 1u)) < (kUp - kLo - 1u);     // 1e-5 < r2~ < 1 - 1e-5
-    const bool unsure = !accept && rb <= kTop;              // r2~ <= 1e-5, or within 1e-5 of 1: fp32 cannot tell
-    if (__ballot(unsure)) {   // wave-uniform on purpose: a real branch around the double-precision test, taken ~1e-3 of the time
-      if (unsure) {
+    uint64_t am = __builtin_amdgcn_ballot_w64((rb - (kLo + 1u)) < (kUp - kLo - 1u));   // accept: 1e-5 < r2~ < 1 - 1e-5
+    const uint64_t um = __builtin_amdgcn_ballot_w64(rb <= kTop) & ~am;   // unsure: r2~ <= 1e-5, or within 1e-5 of 1: fp32 cannot tell
+    if (um) {   // wave-uniform on purpose: a real branch around the double-precision test, taken ~1e-3 of the time
+      bool ex = false;
+      if (__builtin_amdgcn_inverse_ballot_w64(um)) {
         uint32_t t = before;
         asm volatile("" : "+v"(t));   // pins the double-precision test inside the branch
         double x, y, r2;
         polar_candidate(t, x, y, r2);
-        accept = !(r2 > 1.0 || r2 == 0.0);
+        ex = !(r2 > 1.0 || r2 == 0.0);
       }
+      am |= __builtin_amdgcn_ballot_w64(ex);
     }
-    if (accept) {   // moves under the execution mask (the asm keeps the compiler from turning them into selects)
+    if (__builtin_amdgcn_inverse_ballot_w64(am)) {   // moves under the execution mask (the asm keeps the compiler from turning them into selects)
       asm volatile("v_mov_b32 %0, %1\n\tv_mov_b32 %1, %2\n\tv_mov_b32 %2, %3" : "+&v"(st0), "+&v"(st1), "+&v"(st2) : "v"(before));   // early-clobber: `before` is read last and must not share a register with an output
-      got++;
     }
-    if (got >= 3) break;
+    m3 |= m2 & am; m2 |= m1 & am; m1 |= am;
+    if (__builtin_amdgcn_inverse_ballot_w64(m3)) break;
   }
 #else
   st0 = s; st1 = s; st2 = s;   // engine word before the 1st / 2nd / 3rd accepted candidate
@@ -995,8 +1023,19 @@ afe_step_kernel(const StepView<R> v, const DevParams<R> P, const DevLogic G) {
 }
 
 // heterogeneous ensemble: type tables staged into LDS, one record per lane
+// The table kernels with the libstdc++ noise and the logic sit right at a register step (fp32: 128 vector registers, four
+// waves per SIMD; fp64: 246-252, two waves), and two registers more in the shared noise code would cost them a wave: they
+// are held at the waves they have.  Not the ones with both wrenches (fp32 134; fp64 256, which takes 258 now and would
+// spill two registers to scratch if held), and everything else is left to the compiler (1 = no bound).
 template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool BUF>
-__global__ void __launch_bounds__(256)
+constexpr int table_min_waves() {
+  constexpr bool at_a_register_step = NOISE == 1 && LOGIC && BUF;   // libstdc++ noise + logic, buffer addressing
+  constexpr bool both_wrenches = FEXT && TEXT;
+  if (!at_a_register_step || both_wrenches) return 1;                 // no bound
+  return sizeof(R) == 4 ? 4 : 2;
+}
+template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool BUF>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(table_min_waves<R, FEXT, TEXT, NOISE, LOGIC, BUF>())))
 afe_step_kernel_table(const StepView<R> v) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int words_p = v.n_types * (int)(sizeof(DevParams<R>) / 4);
@@ -1271,6 +1310,17 @@ constexpr int persistent_min_waves() { return sizeof(R) != 4 ? 1 : (!RESIDENT ? 
 // workgroup, 24 of them per CU at six waves per SIMD (129 KB of 160).  Every other instantiation reads them as before.
 template <typename R, bool FEXT, bool LOGIC, bool RESIDENT>
 constexpr bool persist_holds() { return sizeof(R) == 4 && FEXT && !LOGIC && !RESIDENT; }
+// The kernel-argument segment of the resident grid (PersistKernarg<R> is its layout: tests/test_kernel_resources.py) through
+// the segment pointer -- not the address of a by-value argument, which would make a private copy.  The empty asm makes the
+// pointer a new value at every call, so nothing read through it is hoisted out of the caller's loop and kept in registers.
+// The cast to a generic reference is folded back to the constant address space once this is inlined: the reads are
+// s_load (make asm).
+template <typename R>
+__device__ __forceinline__ const PersistKernarg<R> &persist_kernarg() {
+  const __attribute__((address_space(4))) char *p = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const PersistKernarg<R> *)p;
+}
 template <typename R, bool FEXT, int NOISE, bool LOGIC, bool RESIDENT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(persistent_min_waves<R, LOGIC, RESIDENT>())))
 afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const DevLogic G_arg, const PersistArgs a) {
@@ -1296,6 +1346,11 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
   const DevParams<R> &P = lds_params ? P_lds : P_arg;
   const DevLogic &G = lds_params ? G_lds : G_arg;
   const int w = (int)blockIdx.x - 1;
+  // Which instantiations re-read their arguments in the one-step loops below (the comment there): the headline's, the one
+  // it was measured on at every size (tools/README.md).  Its counter-noise sibling gains the most where vector issue bounds
+  // the step (262 144 vehicles 3.42 -> 2.60 us) but loses 3 % at 4 096 vehicles and 2 % at 2^20, and choosing by chunks
+  // per worker at run time puts both bodies into one kernel, which spills to scratch; the others were not measured.
+  constexpr bool RELOADS = AFE_KERNARG_RELOAD && NOISE == 1 && persist_holds<R, FEXT, LOGIC, RESIDENT>();
   u64_t s = a.start;
   u64_t t_wait = ticks100();
   u64_t tick_no = v.tick_base;                       // logic ticks so far (the counter policy's sample address)
@@ -1426,19 +1481,27 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
       t_wait = ticks100();
       continue;
     }
+    // Where RELOADS (above) the grid reads its wave-uniform constants -- the view, the parameter record, the hand-shake arguments --
+    // from the kernel-argument segment again in every step and every chunk (persist_kernarg) instead of keeping ~100 dwords
+    // alive across the poll loop: 106 scalar registers do not hold them beside the loop state, and every value parked in a
+    // lane of a vector register comes back through a v_readlane, a vector instruction.  Vector issue is what bounds the
+    // step while the working set lives in the L2s (131 072 - 262 144 vehicles); at 2^20 the bytes set it.
     for (int k = 0; k < run; k++) {
-      persist_set_priority(a, run - k, run);
+      const PersistKernarg<R> *const ks = RELOADS ? &persist_kernarg<R>() : nullptr;
+      const StepView<R> &vs = RELOADS ? ks->v : v;
+      const PersistArgs &as = RELOADS ? ks->a : a;
+      persist_set_priority(as, run - k, run);
       const u64_t tick = (ticks >> k) & 1ull;                              // wave-uniform (scalar)
-      if (a.gust_period_us) {
-        while (t_us >= gust_next_us) { gust_epoch++; gust_next_us += a.gust_period_us; }
+      if (as.gust_period_us) {
+        while (t_us >= gust_next_us) { gust_epoch++; gust_next_us += as.gust_period_us; }
         if (gust_epoch != gust_in_slab) {
-          for (int j = 0, c = w; c < a.n_chunks; j++, c += a.n_workers) {
+          for (int j = 0, c = w; c < as.n_chunks; j++, c += as.n_workers) {
             const int64_t i = (int64_t)c * 64 + lane;
-            if (i < v.n) {
+            if (i < vs.n) {
               R f[3];
-              gust_force<R>(a.gust_seed, (uint64_t)(v.first_global + i), a.gust_n_global, gust_epoch, a.gust_sigma_max, f);
-              R *slab = const_cast<R *>(v.ext_force);
-              slab[i] = f[0]; slab[v.stride + i] = f[1]; slab[2 * v.stride + i] = f[2];
+              gust_force<R>(as.gust_seed, (uint64_t)(vs.first_global + i), as.gust_n_global, gust_epoch, as.gust_sigma_max, f);
+              R *slab = const_cast<R *>(vs.ext_force);
+              slab[i] = f[0]; slab[vs.stride + i] = f[1]; slab[2 * vs.stride + i] = f[2];
               if (HOLDS && hold && j < AFE_PERSIST_HELD_SLOTS) {
 #pragma unroll
                 for (int k = 0; k < 3; k++) held_lds[0].v[j][4 + k][lane] = (float)f[k];
@@ -1447,13 +1510,18 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
           }
           gust_in_slab = gust_epoch;
         }
-        t_us += a.dt_us;
+        t_us += as.dt_us;
       }
-      for (int j = 0, c = w; c < a.n_chunks; j++, c += a.n_workers) {
+      for (int j = 0, c = w;; j++) {
+        const PersistKernarg<R> *const kc = RELOADS ? &persist_kernarg<R>() : nullptr;
+        const StepView<R> &vc = RELOADS ? kc->v : v;
+        const PersistArgs &ac = RELOADS ? kc->a : a;
+        if (c >= ac.n_chunks) break;
         const int64_t i = (int64_t)c * 64 + lane;
-        if (i < v.n)
-          run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true, false, 0, HOLDS>(v, P, G, i, tick, 1, tick_no, HOLDS ? &held_lds[0] : nullptr,
-                                                                                 hold && j < AFE_PERSIST_HELD_SLOTS ? j : -1);
+        if (i < vc.n)
+          run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true, false, 0, HOLDS>(vc, RELOADS ? kc->P : P, RELOADS ? kc->G : G, i, tick, 1, tick_no,
+                                                                                 HOLDS ? &held_lds[0] : nullptr, hold && j < AFE_PERSIST_HELD_SLOTS ? j : -1);
+        c += ac.n_workers;
       }
       tick_no += tick;
     }
