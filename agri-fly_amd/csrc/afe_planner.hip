@@ -275,7 +275,7 @@ __device__ bool input_feasible(const Cand &k, const PlannerConfig &cfg) {
       if (r == SEC_FEASIBLE) break;
       if (r != SEC_SPLIT) return false;
       const double tHalf = (t1 + t2) / 2;
-      if (sp >= 24) return false;
+      if (sp >= 24) return false;   // (never: plan_impl refuses a min_section_time that allows 23 levels, afe_planner_api.cpp)
       stack_t1[sp] = tHalf;   // second half waits
       stack_t2[sp] = t2;
       sp++;

@@ -124,6 +124,16 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
   if ((int64_t)((cfg->width + 63) / 64) * cfg->height * 8 > 65536 || (int64_t)cfg->width * cfg->height >= (1 << 24))
     return AFE_ERR_OUT_OF_RANGE;
   if (depth_on_device && ((uintptr_t)depth_images & 15u)) return AFE_ERR_INVALID_ARG;
+  // CheckInputFeasibility bisects a candidate's duration until a section is shorter than min_section_time
+  // (RapidTrajectoryGenerator.cpp:130-145); the kernel keeps the pending halves on a stack of 24 (input_feasible), which
+  // holds for every section tree of fewer than 23 levels: refuse what could go deeper
+  {
+    if (!(cfg->min_section_time > 0)) return AFE_ERR_OUT_OF_RANGE;
+    double longest = 0;
+    for (int64_t k = 0; k < (int64_t)n_tables * n_candidates; k++)
+      if (samples[4 * k + 3] > longest) longest = samples[4 * k + 3];
+    if (!(longest / cfg->min_section_time < 8388608.0)) return AFE_ERR_OUT_OF_RANGE;
+  }
   if (cfg->focal_length * cfg->planning_vehicle_radius / cfg->depth_scale >= (double)(1 << 22)) return AFE_ERR_OUT_OF_RANGE;
   if (image_index)
     for (int64_t i = 0; i < n; i++) if (image_index[i] < 0 || image_index[i] >= n_images) return AFE_ERR_OUT_OF_RANGE;

@@ -316,7 +316,7 @@ typedef struct afe_planner_config {
   double min_thrust, max_thrust;     /* [m/s^2]; reference defaults 5, 30 (DepthImagePlanner.cpp:43-44) */
   double max_ang_vel;                /* [rad/s]; default 20 */
   double max_velocity;               /* [m/s]; default 5 */
-  double min_section_time;           /* [s]; default 0.02 */
+  double min_section_time;           /* [s]; default 0.02; > 0 and above the longest sample's duration / 2^23 (below) */
   int max_pyramids;                  /* per plan (SetMaxNumberOfPyramids); also sizes the scratch */
   int pixel_buffer;                  /* _pyramidSearchPixelBuffer = 2 */
   int cost_type;                     /* 0: ExplorationCost, -dir.pos(T)/T (DepthImagePlanner.hpp:476-506)
@@ -347,7 +347,13 @@ int afe_planner_samples(uint32_t seed, int width, int height, int n_candidates, 
  *   out[n]; flags [n][n_candidates] or NULL: TrajectoryTestResult bits per candidate
  *   (1 LowCost, 2 DynamicsFeasible, 4 VelocityAdmissible, 8 CollisionFree).
  * Image size: ceil(width/64) * height <= 8192 (one bit per pixel is kept in LDS;
- * e.g. 640x480, 1024x512), else AFE_ERR_OUT_OF_RANGE. */
+ * e.g. 640x480, 1024x512), else AFE_ERR_OUT_OF_RANGE.
+ * cfg->min_section_time: the input-feasibility test halves a candidate's duration
+ * until a section is shorter than this, and the kernel holds at most 24 pending
+ * halves where the reference recurses without a limit.  So that no candidate can
+ * reach that limit, min_section_time <= 0 and max(sample duration) /
+ * min_section_time >= 2^23 are refused with AFE_ERR_OUT_OF_RANGE (for 3 s
+ * candidates: anything below 0.36 us). */
 int afe_rappids_plan(int device, const afe_planner_config *cfg, int64_t n, const uint16_t *depth_images,
                      int64_t n_images, const int32_t *image_index, const double *vel0, const double *acc0,
                      const double *grav, const double *cost_vec, const double *samples, int n_tables,

@@ -10,6 +10,27 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 afa = importlib.import_module("agri-fly_amd")
 from oracle import oracle_py as ora
 
+def explained_by_nudge(args, same):
+    """args: ora.planner_run's arguments of a plan the device answered differently; same(res, rflags): is this the device's
+    answer?  Does the checker itself land on it when ONE of its acos / cos / pow results moves by an ulp or two (libm
+    implementations differ by that much)?  Returns ((call, ulps) or None, number of such calls in the plan)."""
+    ora.planner_nudge(-1, 0)
+    ora.planner_run(*args)
+    calls = ora.planner_nudge_calls()
+    explained = None
+    for j in range(calls):
+        for u in (1, -1, 2, -2):
+            ora.planner_nudge(j, u)
+            res, rflags = ora.planner_run(*args)
+            if same(res, rflags):
+                explained = (j, u)
+                break
+        if explained:
+            break
+    ora.planner_nudge(-1, 0)
+    return explained, calls
+
+
 def run_campaign(per_case=2000, scene_seeds=(11, 12)):
     cases = [(320, 240, 160.0), (192, 144, 96.0), (200, 150, 100.0), (256, 192, 128.0)]
     hard = soft = total = unexplained = 0
@@ -57,23 +78,11 @@ def run_campaign(per_case=2000, scene_seeds=(11, 12)):
             # results moves by an ulp or two?  (libm implementations differ by that much)
             for i in bad:
                 args = (ocfg, images[idx[i]], vel0[:, i], acc0[:, i], grav[:, i], tables[tab[i]])
-                ora.planner_nudge(-1, 0)
-                ora.planner_run(*args)
-                calls = ora.planner_nudge_calls()
                 o = out[i]
-                explained = None
-                for j in range(calls):
-                    for u in (1, -1, 2, -2):
-                        ora.planner_nudge(j, u)
-                        res, rflags = ora.planner_run(*args)
-                        if (o.found, o.best_index) == (res.found, res.best_index) and np.array_equal(flags[i], rflags) and \
-                                (o.n_cost_checks, o.n_collision_checks, o.n_velocity_checks, o.n_collision_free) == \
-                                (res.n_cost_checks, res.n_collision_checks, res.n_velocity_checks, res.n_collision_free):
-                            explained = (j, u)
-                            break
-                    if explained:
-                        break
-                ora.planner_nudge(-1, 0)
+                explained, calls = explained_by_nudge(args, lambda res, rflags: (o.found, o.best_index) == (res.found, res.best_index) and
+                                                      np.array_equal(flags[i], rflags) and
+                                                      (o.n_cost_checks, o.n_collision_checks, o.n_velocity_checks, o.n_collision_free) ==
+                                                      (res.n_cost_checks, res.n_collision_checks, res.n_velocity_checks, res.n_collision_free))
                 unexplained += explained is None
                 print("   plan %d: %d transcendental calls; checker reproduces the device's answer with call %s nudged by %s ulp"
                       % (i, calls, *(explained if explained else ("NONE", "-"))), flush=True)

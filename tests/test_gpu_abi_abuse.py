@@ -184,6 +184,17 @@ refused(plan(n=-1), "plan of -1 planners")
 refused(plan(n_images=1), "two planners, one image, no index")
 refused(plan(n_cand=0), "plan with 0 candidates")
 refused(plan(n_cand=-5), "plan with -5 candidates")
+import copy
+def with_section_time(t):
+    c = copy.copy(cfg)
+    c.min_section_time = t
+    return c
+longest = samples[:, 3].max()
+refused(plan(config=with_section_time(0.0)), "plan with min_section_time 0")
+refused(plan(config=with_section_time(-0.02)), "plan with a negative min_section_time")
+refused(plan(config=with_section_time(float("nan"))), "plan with min_section_time NaN")
+refused(plan(config=with_section_time(longest / 2 ** 23)), "plan whose sections could be halved 23 times")
+answered(plan(config=with_section_time(longest / 2 ** 23 * (1 + 1e-9))), "plan whose sections can be halved 22 times")
 answered(plan(n=0), "plan of 0 planners")
 again = afa.plans_as_array(afa.rappids_plan(cfg, img, z, z, z - [[0], [0], [9.81]], samples)[0])
 assert good.tobytes() == again.tobytes()
