@@ -27,6 +27,9 @@ from .engine import (  # noqa: F401
     ContactMonitor,
     GROUP_STATS_DTYPE,
     GroupStats,
+    PATH_CLEARANCE_DTYPE,
+    PLAN_DTYPE,
+    PathClearance,
     StatsMonitor,
     Comm,
     DeviceBuffer,
@@ -51,6 +54,7 @@ from .engine import (  # noqa: F401
     library,
     library_path,
     params_from_type,
+    path_sample_points,
     plan_ticks,
     planner_default_config,
     planner_release_scratch,

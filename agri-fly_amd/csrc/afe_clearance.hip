@@ -60,12 +60,42 @@
 //
 // The walk's stack lives in LDS as [level][lane] (32 x 256 x 4 B = 32 KB per block, conflict-free: a lane only ever touches
 // its own column); a runtime-indexed private array would go to scratch.  Not covered: swept tests between two updates (see the header).
+//
+// PATH CLEARANCE (afe_clearance_paths, afe_clearance_plans_engine; tests/path_checker.py restates it on top of the checker
+// above).  Same rules: IEEE double, contraction off, + - * / and comparisons, the order below is the contract.
+//   A path: coeffs c[6][3] (t^5 .. t^0 per axis, the layout of afe_plan_output::coeffs), a time range (t_begin, t_end),
+//   optionally an origin o[3] and a row-major matrix R[9].  K = n_samples, 2 <= K <= 4096.
+//   sample time:   t_k = t_begin + (t_end - t_begin) * ((double)k / (double)(K - 1))  for k < K - 1;   t_{K-1} = t_end exactly
+//   sample point:  per axis, Horner:  p = c[0];  p = p*t + c[j]  for j = 1 .. 5
+//        with R:      w.x = o.x + ((R0*p.x + R1*p.y) + R2*p.z),  w.y and w.z with rows 1 and 2
+//        without R:   w = o + p;     without o either:  w = p   (no zero is added: a -0 stays -0)
+//   per sample:    (d2_k, tri_k, closest_k) = the UNBOUNDED point query above at w  (non-finite w: +inf, -1, NaN)
+//   the record (afe_path_clearance), with radius2 = radius*radius and max_dist2 = max_dist*max_dist formed once on the host:
+//        n_nonfinite  = #{k : w has a non-finite coordinate}
+//        n_hit        = #{k : d2_k <= radius2};   k_first_hit = the lowest such k (-1: none), tri_first_hit = tri of that k,
+//                       t_first_hit = t of that k (NaN: none)
+//        min_dist2    = the smallest d2_k among the samples with d2_k < +inf and d2_k <= max_dist2;  k_min = the lowest k among bitwise-equal
+//                       minima;  tri_min, closest[3], t_min from that sample.  No such sample: +inf, -1, -1, NaN, NaN.
+//   afe_clearance_plans_engine: o = the vehicle's position, R = the camera-to-world matrix of att * mount, both formed with
+//   the arithmetic of afe_camera_pose_kernel (afe_render.hip; restated in path_pose below), the range is [0, tf]; a plan with
+//   found == 0 is not sampled and gets the empty record (+inf, every index -1, NaNs, both counts 0).
+//
+// One wave per path, one sample per lane, batches of 64 samples; four paths per block, so the [32][256] stack carries over;
+// no barrier anywhere.  The sample points only ever exist in registers.  A lane starts its walk with the bound
+// max(radius2, best), best = the wave's smallest d2 of the earlier batches (initially max_dist2), wave-uniform.  No output
+// bit depends on that: a sample is a hit iff its own d2 <= radius2 and the bound never drops below radius2; clr_eval accepts
+// ties at the bound, so a sample at or below the bound gets its exact d2, triangle and closest point; a later sample that
+// only ties the running minimum loses on k; a sample above the bound can be neither.  Reduction per batch by wave
+// operations: min of (d2, lane) by a butterfly, first hit by ballot + first set bit, n_hit by popcount; lane 0 writes the
+// record.  What sampling does NOT cover: between two samples a path can come closer than at both (see the header).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "afe_render.h"   // afe::engine_device_view / afe::engine_stream_device
@@ -242,6 +272,51 @@ __device__ __forceinline__ void clr_test(const CTri *T, double px, double py, do
   clr_eval(T, __float_as_int(h1.z), __float_as_int(h1.w), px, py, pz, b);
 }
 
+// The walk for one finite point, starting from the bound and winner in b: the triangles kept out of the tree, then the tree,
+// nearer child first.  `col` is the lane's column of the block's stack.  Shared by the point query and the path kernel.
+template <bool COUNT>
+__device__ __forceinline__ void clr_walk(const ClrArgs &g, double px, double py, double pz, Best &b, uint32_t (*stack)[kBlock], int col,
+                                         unsigned &n_nodes, unsigned &n_box, unsigned &n_eval) {
+#pragma clang fp contract(off)
+  // S: squared distance to the farthest corner of the scene's box (bounds |p - vertex|^2 for every vertex)
+  const double fx = fmax(fabs(px - g.scene_lo[0]), fabs(px - g.scene_hi[0]));
+  const double fy = fmax(fabs(py - g.scene_lo[1]), fabs(py - g.scene_hi[1]));
+  const double fz = fmax(fabs(pz - g.scene_lo[2]), fabs(pz - g.scene_hi[2]));
+  const double slack = 0x1p-40 * (fx * fx + fy * fy + fz * fz);
+  for (uint32_t k = 0; k < g.n_big; k++) clr_test<COUNT>(g.tris + g.big_first + k, px, py, pz, slack, b, n_box, n_eval);
+  uint32_t cur = g.root_ref;
+  if (cur != kNone) {
+    float4 lo, hi;
+    lo.x = g.root_lo[0]; lo.y = g.root_lo[1]; lo.z = g.root_lo[2]; lo.w = 0.0f;
+    hi.x = g.root_hi[0]; hi.y = g.root_hi[1]; hi.z = g.root_hi[2]; hi.w = 0.0f;
+    if (clr_skip(clr_box_lb(lo, hi, px, py, pz), b.d2, slack)) cur = kNone;
+  }
+  int sp = 0;
+  while (cur != kNone) {                 // bounded: every node is entered at most once
+    if (cur & kLeafBit) {
+      const uint32_t first = cur & kFirstMask, cnt = (cur >> 28) & 7u;
+      for (uint32_t k = 0; k < cnt; k++) clr_test<COUNT>(g.tris + first + k, px, py, pz, slack, b, n_box, n_eval);
+      cur = kNone;
+    } else {
+      if (COUNT) n_nodes++;
+      const float4 *rec = reinterpret_cast<const float4 *>(g.nodes + cur);
+      const float4 lo0 = rec[0], hi0 = rec[1], lo1 = rec[2], hi1 = rec[3];
+      const double lb0 = clr_box_lb(lo0, hi0, px, py, pz), lb1 = clr_box_lb(lo1, hi1, px, py, pz);
+      const bool go0 = !clr_skip(lb0, b.d2, slack), go1 = !clr_skip(lb1, b.d2, slack);
+      const uint32_t ref0 = (uint32_t)__float_as_int(lo0.w), ref1 = (uint32_t)__float_as_int(lo1.w);
+      if (go0 && go1) {
+        const bool near0 = lb0 <= lb1;
+        if (sp < kStack) stack[sp++][col] = near0 ? ref1 : ref0;    // (the builder keeps the depth below kStack)
+        cur = near0 ? ref0 : ref1;
+        continue;
+      }
+      cur = go0 ? ref0 : (go1 ? ref1 : kNone);
+      if (cur != kNone) continue;
+    }
+    if (sp > 0) cur = stack[--sp][col];
+  }
+}
+
 template <bool MONITOR, bool COUNT>
 __global__ void __launch_bounds__(kBlock) afe_clearance_kernel(ClrArgs g) {
 #pragma clang fp contract(off)
@@ -266,43 +341,7 @@ __global__ void __launch_bounds__(kBlock) afe_clearance_kernel(ClrArgs g) {
   b.d2 = g.max_dist2; b.idx = 0x7fffffff; b.cx = nan; b.cy = nan; b.cz = nan;
   unsigned n_nodes = 0, n_box = 0, n_eval = 0;
   if (valid && __builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz)) {
-    // S: squared distance to the farthest corner of the scene's box (bounds |p - vertex|^2 for every vertex)
-    const double fx = fmax(fabs(px - g.scene_lo[0]), fabs(px - g.scene_hi[0]));
-    const double fy = fmax(fabs(py - g.scene_lo[1]), fabs(py - g.scene_hi[1]));
-    const double fz = fmax(fabs(pz - g.scene_lo[2]), fabs(pz - g.scene_hi[2]));
-    const double slack = 0x1p-40 * (fx * fx + fy * fy + fz * fz);
-    for (uint32_t k = 0; k < g.n_big; k++) clr_test<COUNT>(g.tris + g.big_first + k, px, py, pz, slack, b, n_box, n_eval);
-    uint32_t cur = g.root_ref;
-    if (cur != kNone) {
-      float4 lo, hi;
-      lo.x = g.root_lo[0]; lo.y = g.root_lo[1]; lo.z = g.root_lo[2]; lo.w = 0.0f;
-      hi.x = g.root_hi[0]; hi.y = g.root_hi[1]; hi.z = g.root_hi[2]; hi.w = 0.0f;
-      if (clr_skip(clr_box_lb(lo, hi, px, py, pz), b.d2, slack)) cur = kNone;
-    }
-    int sp = 0;
-    while (cur != kNone) {
-      if (cur & kLeafBit) {
-        const uint32_t first = cur & kFirstMask, cnt = (cur >> 28) & 7u;
-        for (uint32_t k = 0; k < cnt; k++) clr_test<COUNT>(g.tris + first + k, px, py, pz, slack, b, n_box, n_eval);
-        cur = kNone;
-      } else {
-        if (COUNT) n_nodes++;
-        const float4 *rec = reinterpret_cast<const float4 *>(g.nodes + cur);
-        const float4 lo0 = rec[0], hi0 = rec[1], lo1 = rec[2], hi1 = rec[3];
-        const double lb0 = clr_box_lb(lo0, hi0, px, py, pz), lb1 = clr_box_lb(lo1, hi1, px, py, pz);
-        const bool go0 = !clr_skip(lb0, b.d2, slack), go1 = !clr_skip(lb1, b.d2, slack);
-        const uint32_t ref0 = (uint32_t)__float_as_int(lo0.w), ref1 = (uint32_t)__float_as_int(lo1.w);
-        if (go0 && go1) {           // the nearer child now, the other one later
-          const bool near0 = lb0 <= lb1;
-          if (sp < kStack) stack[sp++][lane] = near0 ? ref1 : ref0;    // (the builder keeps the depth below kStack)
-          cur = near0 ? ref0 : ref1;
-          continue;
-        }
-        cur = go0 ? ref0 : (go1 ? ref1 : kNone);
-        if (cur != kNone) continue;
-      }
-      if (sp > 0) cur = stack[--sp][lane];
-    }
+    clr_walk<COUNT>(g, px, py, pz, b, stack, lane, n_nodes, n_box, n_eval);
   }
   const bool found = b.idx != 0x7fffffff;
   if (valid) {
@@ -348,6 +387,211 @@ __global__ void __launch_bounds__(kBlock) afe_clearance_reset_kernel(double *min
   min_dist2[first + i] = std::numeric_limits<double>::infinity();
   first_us[first + i] = ~uint64_t(0);
   first_tri[first + i] = -1;
+}
+
+// ---------------------------------------------------------------------------------------
+// path clearance (the definition: file header)
+// ---------------------------------------------------------------------------------------
+constexpr int kPathsPerBlock = kBlock / 64;
+constexpr int kMinSamples = 2, kMaxSamples = 4096;
+constexpr int64_t kMaxPaths = int64_t(1) << 30;       // blocks stay far below 2^31
+
+struct PathArgs {
+  ClrArgs t;                    // the tree's part (nodes .. scene_hi); nothing else of it is read
+  int64_t n_paths;
+  int n_samples;
+  double radius2, max_dist2;
+  // explicit paths, indexed by the path i
+  const double *coeffs;         // [n][6][3]
+  const double *t_range;        // planar [2][n]
+  const double *origin;         // planar [3][n] or NULL
+  const double *rot;            // planar [9][n] or NULL
+  // plans of the engine's vehicles first + i
+  const afe_plan_output *plans; // [n]
+  const void *pos, *att;        // the engine's slabs: planar, `stride` elements between components
+  const double *anchor_xy;
+  int64_t stride, first;
+  int elem_size;                // 4 or 8
+  double mount[4];
+  afe_path_clearance *out;      // [n]
+  unsigned long long *n_colliding;   // one word, or NULL
+  unsigned long long *stats;    // counting build: [0] nodes visited, [1] triangle box tests, [2] fp64 evaluations
+};
+
+// sample k of K: its time and its world point
+__host__ __device__ __forceinline__ void path_sample(const double (&c)[18], double tb, double te, bool has_o, const double (&o)[3], bool has_r,
+                                                     const double (&R)[9], int k, int K, double &t, double &wx, double &wy, double &wz) {
+#pragma clang fp contract(off)
+  t = k == K - 1 ? te : tb + (te - tb) * ((double)k / (double)(K - 1));
+  double p[3];
+  for (int a = 0; a < 3; a++) {
+    double v = c[a];
+    for (int j = 1; j < 6; j++) v = v * t + c[3 * j + a];
+    p[a] = v;
+  }
+  if (has_r) {
+    wx = o[0] + ((R[0] * p[0] + R[1] * p[1]) + R[2] * p[2]);
+    wy = o[1] + ((R[3] * p[0] + R[4] * p[1]) + R[5] * p[2]);
+    wz = o[2] + ((R[6] * p[0] + R[7] * p[1]) + R[8] * p[2]);
+  } else if (has_o) {
+    wx = o[0] + p[0]; wy = o[1] + p[1]; wz = o[2] + p[2];
+  } else {
+    wx = p[0]; wy = p[1]; wz = p[2];
+  }
+}
+
+// origin and camera-to-world matrix of vehicle v: the arithmetic of afe_camera_pose_kernel (afe_render.hip), operation for operation
+__device__ __forceinline__ void path_pose(const PathArgs &a, int64_t v, double (&o)[3], double (&R)[9]) {
+#pragma clang fp contract(off)
+  double p[3], q[4];
+  if (a.elem_size == 8) {
+    const double *P = (const double *)a.pos, *Q = (const double *)a.att;
+    for (int k = 0; k < 3; k++) p[k] = P[k * a.stride + v];
+    for (int k = 0; k < 4; k++) q[k] = Q[k * a.stride + v];
+  } else {
+    const float *P = (const float *)a.pos, *Q = (const float *)a.att;
+    for (int k = 0; k < 3; k++) p[k] = (double)P[k * a.stride + v];
+    for (int k = 0; k < 4; k++) q[k] = (double)Q[k * a.stride + v];
+  }
+  if (a.anchor_xy) { p[0] = a.anchor_xy[v] + p[0]; p[1] = a.anchor_xy[a.stride + v] + p[1]; }
+  const double *m = a.mount;
+  const double c0 = m[0] * q[0] - m[1] * q[1] - m[2] * q[2] - m[3] * q[3];
+  const double c1 = m[1] * q[0] + m[0] * q[1] + m[3] * q[2] - m[2] * q[3];
+  const double c2 = m[2] * q[0] - m[3] * q[1] + m[0] * q[2] + m[1] * q[3];
+  const double c3 = m[3] * q[0] + m[2] * q[1] - m[1] * q[2] + m[0] * q[3];
+  const double r0 = c0 * c0, r1 = c1 * c1, r2 = c2 * c2, r3 = c3 * c3;
+  o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+  R[0] = r0 + r1 - r2 - r3;
+  R[1] = 2 * c1 * c2 - 2 * c0 * c3;
+  R[2] = 2 * c1 * c3 + 2 * c0 * c2;
+  R[3] = 2 * c1 * c2 + 2 * c0 * c3;
+  R[4] = r0 - r1 + r2 - r3;
+  R[5] = 2 * c2 * c3 - 2 * c0 * c1;
+  R[6] = 2 * c1 * c3 - 2 * c0 * c2;
+  R[7] = 2 * c2 * c3 + 2 * c0 * c1;
+  R[8] = r0 - r1 - r2 + r3;
+}
+
+// smallest (d, l) of the wave in every lane; among equal d the lowest l.  Every lane of the wave takes part.
+__device__ __forceinline__ void wave_min_d2_lane(double &d, int &l) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double od = __shfl_xor(d, off);
+    const int ol = __shfl_xor(l, off);
+    if (od < d || (od == d && ol < l)) { d = od; l = ol; }
+  }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+  return x;
+}
+
+// The kernel's arguments, read where they are used.  Held in scalar registers from the kernel's entry to its end, the two
+// dozen that only the top of a batch or the record's store needs would push the walk's working set into spills; behind a
+// pointer the compiler cannot see through, each is a scalar load from the (cached) argument segment at its use.
+__device__ __forceinline__ const PathArgs &path_args() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  auto p = __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const PathArgs *)p;
+#else
+  __builtin_unreachable();      // (the host pass only parses device code)
+#endif
+}
+
+template <bool ENGINE, bool COUNT>
+__global__ void __launch_bounds__(kBlock) afe_path_clearance_kernel(PathArgs) {      // the one argument: offset 0 of the segment
+#pragma clang fp contract(off)
+  __shared__ uint32_t stack[kStack][kBlock];
+  const PathArgs &a0 = path_args();
+  const int col = threadIdx.x, lane = col & 63;
+  const int64_t path = (int64_t)blockIdx.x * kPathsPerBlock + __builtin_amdgcn_readfirstlane(col >> 6);
+  if (path >= a0.n_paths) return;         // a wave without a path falls through (no barrier below)
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+  const int K = a0.n_samples;
+  const bool sampled = ENGINE ? a0.plans[path].found != 0 : true;
+  double best = a0.max_dist2;             // wave-uniform: the smallest d2 of the batches so far
+  int k_min = -1, tri_min = -1, k_first = -1, tri_first = -1, n_hit = 0, n_nonfinite = 0;
+  double cx = nan, cy = nan, cz = nan, t_min = nan, t_first = nan;
+  unsigned n_nodes = 0, n_box = 0, n_eval = 0;
+  for (int base = 0; sampled && base < K; base += 64) {       // at most 64 batches
+    const int k = base + lane;
+    const bool valid = k < K;
+    // The path's 30-odd wave-uniform values are fetched again for every batch (scalar loads that hit the cache; the pose is a
+    // few dozen operations) instead of being held across the walk, for the same reason as the arguments.
+    const PathArgs &a = path_args();
+    const int64_t pi = path;
+    double c[18], o[3] = {0.0, 0.0, 0.0}, R[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double tb, te;
+    bool has_o, has_r;
+    if (ENGINE) {
+      const afe_plan_output *plan = a.plans + pi;
+      const double *src = &plan->coeffs[0][0];
+#pragma unroll
+      for (int j = 0; j < 18; j++) c[j] = src[j];
+      tb = 0.0; te = plan->tf;
+      has_o = true; has_r = true;
+      path_pose(a, a.first + pi, o, R);
+    } else {
+      const double *src = a.coeffs + 18 * pi;
+#pragma unroll
+      for (int j = 0; j < 18; j++) c[j] = src[j];
+      tb = a.t_range[pi]; te = a.t_range[a.n_paths + pi];
+      has_o = a.origin != nullptr; has_r = a.rot != nullptr;
+      if (has_o) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) o[j] = a.origin[j * a.n_paths + pi];
+      }
+      if (has_r) {
+#pragma unroll
+        for (int j = 0; j < 9; j++) R[j] = a.rot[j * a.n_paths + pi];
+      }
+    }
+    double t, wx, wy, wz;
+    path_sample(c, tb, te, has_o, o, has_r, R, valid ? k : K - 1, K, t, wx, wy, wz);
+    const bool finite = __builtin_isfinite(wx) && __builtin_isfinite(wy) && __builtin_isfinite(wz);
+    Best b;
+    b.d2 = fmax(a.radius2, best); b.idx = 0x7fffffff; b.cx = nan; b.cy = nan; b.cz = nan;
+    if (valid && finite) clr_walk<COUNT>(a.t, wx, wy, wz, b, stack, col, n_nodes, n_box, n_eval);
+    const bool found = b.idx != 0x7fffffff;             // then b.d2 is this sample's own d2, b.idx and b.c its own winner
+    // hits: ballot, first set bit, popcount
+    const unsigned long long hits = __ballot(found && b.d2 <= path_args().radius2);
+    const int first_lane = hits ? __ffsll((long long)hits) - 1 : 0;
+    const int tri_at = __shfl(b.idx, first_lane);
+    const double t_at = __shfl(t, first_lane);
+    if (hits && k_first < 0) { k_first = base + first_lane; tri_first = tri_at; t_first = t_at; }
+    n_hit += __popcll(hits);
+    n_nonfinite += __popcll(__ballot(valid && !finite));
+    // closest approach: (d2, lane) of the batch, then against the batches before (a tie loses: its k is higher)
+    const bool cand = found && b.d2 <= best;
+    double md = cand ? b.d2 : inf;
+    int ml = cand ? lane : 64;
+    wave_min_d2_lane(md, ml);
+    const int src_lane = ml & 63;
+    const int tri_w = __shfl(b.idx, src_lane);
+    const double cx_w = __shfl(b.cx, src_lane), cy_w = __shfl(b.cy, src_lane), cz_w = __shfl(b.cz, src_lane), t_w = __shfl(t, src_lane);
+    if (ml < 64 && (md < best || k_min < 0)) {
+      best = md; k_min = base + ml; tri_min = tri_w; cx = cx_w; cy = cy_w; cz = cz_w; t_min = t_w;
+    }
+  }
+  const PathArgs &a = path_args();
+  if (lane == 0) {
+    afe_path_clearance *r = a.out + path;
+    r->min_dist2 = k_min >= 0 ? best : inf;
+    r->closest[0] = cx; r->closest[1] = cy; r->closest[2] = cz;
+    r->t_min = t_min;
+    r->t_first_hit = t_first;
+    r->k_min = k_min; r->tri_min = tri_min;
+    r->k_first_hit = k_first; r->tri_first_hit = tri_first;
+    r->n_hit = n_hit; r->n_nonfinite = n_nonfinite;
+    if (a.n_colliding && n_hit > 0) atomicAdd(a.n_colliding, 1ull);      // one integer vector atomic per colliding path
+  }
+  if (COUNT) {
+    const unsigned long long s0 = wave_sum(n_nodes), s1 = wave_sum(n_box), s2 = wave_sum(n_eval);
+    if (lane < 3) atomicAdd(a.stats + lane, lane == 0 ? s0 : (lane == 1 ? s1 : s2));
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -533,6 +777,10 @@ struct afe_clearance_map {
   CNode *nodes = nullptr;
   CTri *tris = nullptr;
   ClrArgs base;         // the tree's part of the kernel arguments
+  // afe_clearance_plans_engine's device scratch (plans, records, one counter), grown on demand; calls take turns on it
+  std::mutex scratch_lock;
+  void *scratch = nullptr;
+  size_t scratch_bytes = 0;
 };
 
 struct afe_contact_monitor {
@@ -657,6 +905,7 @@ extern "C" int afe_clearance_map_destroy(afe_clearance_map *m) {
   (void)hipDeviceSynchronize();      // a query on some stream may still be reading the tables
   if (m->nodes) (void)hipFree(m->nodes);
   if (m->tris) (void)hipFree(m->tris);
+  if (m->scratch) (void)hipFree(m->scratch);
   delete m;
   return AFE_OK;
 }
@@ -739,6 +988,181 @@ extern "C" int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, i
       (hipMemcpy(dist2_out, d_d2.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tri_out, d_tri.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
        (closest_out && hipMemcpy(closest_out, d_cl.p, n * 24, hipMemcpyDeviceToHost) != hipSuccess)))
     return AFE_ERR_HIP;
+  return AFE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// path clearance
+// ---------------------------------------------------------------------------------------
+namespace {
+
+bool path_radii_ok(double radius, double max_dist) { return radius > 0.0 && std::isfinite(radius) && radius <= max_dist; }   // NaN fails; +inf max_dist passes
+bool path_samples_ok(int n_samples) { return n_samples >= kMinSamples && n_samples <= kMaxSamples; }
+
+// one launch on `stream`; with kernel_ms, waits for it
+template <bool ENGINE>
+int launch_paths(const PathArgs &a, hipStream_t stream, float *kernel_ms) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) { if (e0) (void)hipEventDestroy(e0); return AFE_ERR_HIP; }
+  if (kernel_ms) (void)hipEventRecord(e0, stream);
+  const dim3 grid((unsigned)((a.n_paths + kPathsPerBlock - 1) / kPathsPerBlock)), block(kBlock);
+  // path_args() reads the argument segment from offset 0: the kernel takes PathArgs by value and nothing else
+  static_assert(std::is_same<decltype(&afe_path_clearance_kernel<ENGINE, false>), void (*)(PathArgs)>::value, "one by-value PathArgs");
+  bool counting = false;
+  if constexpr (!ENGINE) counting = a.stats != nullptr;        // (the counting build serves explicit paths only)
+  if constexpr (!ENGINE) { if (counting) hipLaunchKernelGGL((afe_path_clearance_kernel<false, true>), grid, block, 0, stream, a); }
+  if (!counting) hipLaunchKernelGGL((afe_path_clearance_kernel<ENGINE, false>), grid, block, 0, stream, a);
+  int rc = hipGetLastError() == hipSuccess ? AFE_OK : AFE_ERR_HIP;
+  if (kernel_ms) {
+    (void)hipEventRecord(e1, stream);
+    if (rc == AFE_OK && hipEventSynchronize(e1) != hipSuccess) rc = AFE_ERR_HIP;
+    if (rc == AFE_OK) (void)hipEventElapsedTime(kernel_ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  }
+  return rc;
+}
+
+int paths_args_check(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range, const double *origin, const double *rot,
+                     int n_samples, double radius, double max_dist) {
+  if (!m || n_paths < 0 || !path_radii_ok(radius, max_dist) || (rot && !origin)) return AFE_ERR_INVALID_ARG;
+  if (n_paths > 0 && (!coeffs || !t_range)) return AFE_ERR_INVALID_ARG;
+  if (!path_samples_ok(n_samples) || n_paths > kMaxPaths) return AFE_ERR_OUT_OF_RANGE;
+  return AFE_OK;
+}
+
+// explicit paths: uploads the host arrays, downloads the records (out may be NULL: discarded)
+int run_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range, const double *origin, const double *rot,
+              int n_samples, double radius, double max_dist, afe_path_clearance *out, int64_t *n_colliding, float *kernel_ms, uint64_t *stats) {
+  if (hipSetDevice(m->device) != hipSuccess) return AFE_ERR_HIP;
+  const size_t n = (size_t)n_paths;
+  DevMem d_c, d_t, d_o, d_r, d_out, d_words;
+  if (!d_c.alloc(n * 144) || !d_t.alloc(n * 16) || (origin && !d_o.alloc(n * 24)) || (rot && !d_r.alloc(n * 72)) || !d_out.alloc(n * sizeof(afe_path_clearance)) ||
+      !d_words.alloc(32)) {
+    (void)hipGetLastError();
+    return AFE_ERR_HIP;
+  }
+  if (hipMemcpy(d_c.p, coeffs, n * 144, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_t.p, t_range, n * 16, hipMemcpyHostToDevice) != hipSuccess ||
+      (origin && hipMemcpy(d_o.p, origin, n * 24, hipMemcpyHostToDevice) != hipSuccess) ||
+      (rot && hipMemcpy(d_r.p, rot, n * 72, hipMemcpyHostToDevice) != hipSuccess) || hipMemset(d_words.p, 0, 32) != hipSuccess)
+    return AFE_ERR_HIP;
+  PathArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.t = m->base;
+  a.n_paths = n_paths; a.n_samples = n_samples;
+  a.radius2 = radius * radius; a.max_dist2 = max_dist * max_dist;
+  a.coeffs = (const double *)d_c.p; a.t_range = (const double *)d_t.p; a.origin = (const double *)d_o.p; a.rot = (const double *)d_r.p;
+  a.out = (afe_path_clearance *)d_out.p;
+  a.n_colliding = (unsigned long long *)d_words.p;
+  a.stats = stats ? (unsigned long long *)d_words.p + 1 : nullptr;
+  float ms = 0;
+  const int rc = launch_paths<false>(a, nullptr, &ms);
+  if (rc != AFE_OK) return rc;
+  if (kernel_ms) *kernel_ms = ms;
+  unsigned long long words[4];
+  if ((out && hipMemcpy(out, d_out.p, n * sizeof(afe_path_clearance), hipMemcpyDeviceToHost) != hipSuccess) ||
+      hipMemcpy(words, d_words.p, 32, hipMemcpyDeviceToHost) != hipSuccess)
+    return AFE_ERR_HIP;
+  if (n_colliding) *n_colliding = (int64_t)words[0];
+  if (stats) {
+    for (int k = 0; k < 3; k++) stats[k] = words[1 + k];
+    stats[3] = (uint64_t)n_paths * (uint64_t)n_samples;
+  }
+  return AFE_OK;
+}
+
+}  // namespace
+
+extern "C" int afe_path_sample_points(const double *coeffs18, double t_begin, double t_end, const double *origin3, const double *rot9,
+                                      int n_samples, double *t_out, double *xyz_out) {
+  if (!coeffs18 || !t_out || !xyz_out || (rot9 && !origin3)) return AFE_ERR_INVALID_ARG;
+  if (!path_samples_ok(n_samples)) return AFE_ERR_OUT_OF_RANGE;
+  double c[18], o[3] = {0.0, 0.0, 0.0}, R[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < 18; k++) c[k] = coeffs18[k];
+  if (origin3) for (int k = 0; k < 3; k++) o[k] = origin3[k];
+  if (rot9) for (int k = 0; k < 9; k++) R[k] = rot9[k];
+  const size_t K = (size_t)n_samples;
+  for (int k = 0; k < n_samples; k++)
+    path_sample(c, t_begin, t_end, origin3 != nullptr, o, rot9 != nullptr, R, k, n_samples, t_out[k], xyz_out[k], xyz_out[K + k], xyz_out[2 * K + k]);
+  return AFE_OK;
+}
+
+extern "C" int afe_clearance_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range, const double *origin,
+                                   const double *rot, int n_samples, double radius, double max_dist, afe_path_clearance *out, int64_t *n_colliding,
+                                   float *kernel_ms) {
+  const int rc = paths_args_check(m, n_paths, coeffs, t_range, origin, rot, n_samples, radius, max_dist);
+  if (rc != AFE_OK) return rc;
+  if (n_paths > 0 && !out) return AFE_ERR_INVALID_ARG;
+  if (n_paths == 0) { if (n_colliding) *n_colliding = 0; return AFE_OK; }
+  return run_paths(m, n_paths, coeffs, t_range, origin, rot, n_samples, radius, max_dist, out, n_colliding, kernel_ms, nullptr);
+}
+
+extern "C" int afe_clearance_paths_stats(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range, const double *origin,
+                                         const double *rot, int n_samples, double radius, double max_dist, uint64_t stats[4], float *kernel_ms) {
+  const int rc = paths_args_check(m, n_paths, coeffs, t_range, origin, rot, n_samples, radius, max_dist);
+  if (rc != AFE_OK) return rc;
+  if (n_paths <= 0 || !stats) return AFE_ERR_INVALID_ARG;
+  return run_paths(m, n_paths, coeffs, t_range, origin, rot, n_samples, radius, max_dist, nullptr, nullptr, kernel_ms, stats);
+}
+
+extern "C" int afe_clearance_plans_engine(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t count, const double mount[4],
+                                          const afe_plan_output *plans, int n_samples, double radius, double max_dist, afe_path_clearance *out,
+                                          int64_t *n_colliding, float *kernel_ms) {
+  if (!e || !m || first < 0 || count < 0 || !path_radii_ok(radius, max_dist)) return AFE_ERR_INVALID_ARG;
+  if (count > 0 && (!plans || !out)) return AFE_ERR_INVALID_ARG;
+  if (!path_samples_ok(n_samples)) return AFE_ERR_OUT_OF_RANGE;
+  {
+    int64_t first_global = 0, n = 0;
+    afe::engine_shard(e, &first_global, &n);
+    if (first > n || count > n - first || count > kMaxPaths) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
+    if (count == 0) { if (n_colliding) *n_colliding = 0; return AFE_OK; }   // a valid range of nothing: answered before the engine is touched
+  }
+  hipStream_t stream = nullptr;
+  int device = 0;
+  afe::engine_stream_device(e, (void **)&stream, &device);     // (ends a resident grid, as the camera does)
+  if (device != m->device) return AFE_ERR_INVALID_ARG;
+  afe_device_view view;
+  view.struct_bytes = sizeof(view);
+  int rc = afe::engine_device_view(e, &view);
+  if (rc != AFE_OK) return rc;
+  if (first > view.n_vehicles || count > view.n_vehicles - first) return AFE_ERR_OUT_OF_RANGE;
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  const size_t n = (size_t)count, plan_bytes = n * sizeof(afe_plan_output), rec_bytes = n * sizeof(afe_path_clearance);
+  std::lock_guard<std::mutex> turn(m->scratch_lock);
+  if (m->scratch_bytes < plan_bytes + rec_bytes + 8) {
+    if (hipStreamSynchronize(stream) != hipSuccess) return AFE_ERR_HIP;
+    if (m->scratch) (void)hipFree(m->scratch);
+    m->scratch = nullptr; m->scratch_bytes = 0;
+    if (hipMalloc(&m->scratch, plan_bytes + rec_bytes + 8) != hipSuccess) { (void)hipGetLastError(); m->scratch = nullptr; return AFE_ERR_HIP; }
+    m->scratch_bytes = plan_bytes + rec_bytes + 8;
+  }
+  char *base = (char *)m->scratch;        // records | plans | counter: every part 8-byte aligned
+  PathArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.t = m->base;
+  a.n_paths = count; a.n_samples = n_samples;
+  a.radius2 = radius * radius; a.max_dist2 = max_dist * max_dist;
+  a.out = (afe_path_clearance *)base;
+  a.plans = (const afe_plan_output *)(base + rec_bytes);
+  a.n_colliding = (unsigned long long *)(base + rec_bytes + plan_bytes);
+  a.pos = view.pos; a.att = view.att; a.anchor_xy = view.pos_anchor_xy; a.stride = view.stride; a.first = first; a.elem_size = view.state_elem_size;
+  static const double identity[4] = {1.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < 4; k++) a.mount[k] = (mount ? mount : identity)[k];
+  // the plans are the only upload
+  // (an error below leaves work in flight on the scratch and on `out`: wait for it before the next caller gets its turn)
+  const auto fail = [&](int status) { (void)hipStreamSynchronize(stream); return status; };
+  if (hipMemcpyAsync((void *)a.plans, plans, plan_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipMemsetAsync(a.n_colliding, 0, 8, stream) != hipSuccess)
+    return fail(AFE_ERR_HIP);
+  float ms = 0;
+  rc = launch_paths<true>(a, stream, kernel_ms ? &ms : nullptr);
+  if (rc != AFE_OK) return fail(rc);
+  if (kernel_ms) *kernel_ms = ms;
+  unsigned long long colliding = 0;
+  if (hipMemcpyAsync(out, a.out, rec_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipMemcpyAsync(&colliding, a.n_colliding, 8, hipMemcpyDeviceToHost, stream) != hipSuccess)
+    return fail(AFE_ERR_HIP);
+  if (hipStreamSynchronize(stream) != hipSuccess) return AFE_ERR_HIP;
+  if (n_colliding) *n_colliding = (int64_t)colliding;
   return AFE_OK;
 }
 

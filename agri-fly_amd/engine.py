@@ -51,6 +51,7 @@ ABI_FUNCTIONS = [
     "afe_has_dev_hooks", "afe_persistent_kernarg_layout", "afe_group_set_staged_copies",
     "afe_clearance_map_create", "afe_clearance_map_destroy", "afe_clearance_map_info", "afe_clearance_check_hierarchy",
     "afe_clearance_query", "afe_clearance_query_stats", "afe_clearance_query_engine",
+    "afe_path_sample_points", "afe_clearance_paths", "afe_clearance_paths_stats", "afe_clearance_plans_engine",
     "afe_contact_monitor_create", "afe_contact_monitor_update", "afe_contact_monitor_get", "afe_contact_monitor_reset",
     "afe_contact_monitor_destroy",
     "afe_stats_check_layout", "afe_stats_create", "afe_stats_destroy", "afe_stats_info", "afe_stats_set_reference",
@@ -375,6 +376,10 @@ def library():
         "afe_clearance_query": [vp, i64, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_float)],
         "afe_clearance_query_stats": [vp, i64, vp, C.c_double, vp, C.POINTER(C.c_float)],
         "afe_clearance_query_engine": [eng, vp, i64, i64, C.c_double, vp, vp, vp, ci, C.POINTER(C.c_float)],
+        "afe_path_sample_points": [vp, C.c_double, C.c_double, vp, vp, ci, vp, vp],
+        "afe_clearance_paths": [vp, i64, vp, vp, vp, vp, ci, C.c_double, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "afe_clearance_paths_stats": [vp, i64, vp, vp, vp, vp, ci, C.c_double, C.c_double, vp, C.POINTER(C.c_float)],
+        "afe_clearance_plans_engine": [eng, vp, i64, i64, vp, vp, ci, C.c_double, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
         "afe_contact_monitor_create": [eng, vp, C.c_double, C.c_double, C.POINTER(vp)],
         "afe_contact_monitor_update": [vp, C.POINTER(i64), C.POINTER(i64)],
         "afe_contact_monitor_get": [vp, i64, i64, vp, vp, vp],
@@ -655,6 +660,41 @@ def _status(rc):
         raise AfeError(rc, library().afe_status_string(rc).decode())
 
 
+class PathClearance(C.Structure):
+    """afe_path_clearance: what one sampled path did against the mesh (8-byte members only, 96 bytes)."""
+    _fields_ = [("min_dist2", C.c_double), ("closest", C.c_double * 3), ("t_min", C.c_double), ("t_first_hit", C.c_double),
+                ("k_min", C.c_int64), ("tri_min", C.c_int64), ("k_first_hit", C.c_int64), ("tri_first_hit", C.c_int64),
+                ("n_hit", C.c_int64), ("n_nonfinite", C.c_int64)]
+
+
+PATH_CLEARANCE_DTYPE = np.dtype([("min_dist2", np.float64), ("closest", np.float64, (3,)), ("t_min", np.float64),
+                                 ("t_first_hit", np.float64), ("k_min", np.int64), ("tri_min", np.int64),
+                                 ("k_first_hit", np.int64), ("tri_first_hit", np.int64), ("n_hit", np.int64),
+                                 ("n_nonfinite", np.int64)])
+
+
+def _opt_f64(a, shape):
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    assert a.shape == shape, (a.shape, shape)
+    return a, a.ctypes.data
+
+
+def path_sample_points(coeffs, t_begin, t_end, origin=None, rot=None, n_samples=64):
+    """Host-only: the sample times [K] and world points [3, K] of one path (coeffs [6, 3], t^5 .. t^0 per axis; origin [3]
+    and row-major rot [9] or [3, 3] optional) by the definition's expressions (csrc/afe_clearance.hip)."""
+    c = np.ascontiguousarray(coeffs, dtype=np.float64)
+    assert c.shape == (6, 3)
+    o, o_ptr = _opt_f64(origin, (3,))
+    r, r_ptr = _opt_f64(None if rot is None else np.asarray(rot, np.float64).reshape(-1), (9,))
+    k = max(int(n_samples), 0)
+    t, xyz = np.empty(k), np.empty((3, k))
+    _status(library().afe_path_sample_points(c.ctypes.data, float(t_begin), float(t_end), o_ptr, r_ptr, int(n_samples),
+                                             t.ctypes.data, xyz.ctypes.data))
+    return t, xyz
+
+
 class ClearanceMap:
     """afe_clearance_map: a static triangle mesh (world frame, metres) + its own hierarchy in HBM, answering
     "how far is this point from the mesh" (squared distances; see the header)."""
@@ -721,6 +761,58 @@ class ClearanceMap:
         _status(library().afe_clearance_query_engine(ensemble.handle, self._h, int(first), int(count), float(max_dist),
                                                      args[0], args[1], args[2], is_dev, C.byref(ms)))
         return (d2, tri, cl, ms.value) if out is None else ms.value
+
+    @staticmethod
+    def _path_arrays(coeffs, t_range, origin, rot):
+        c = np.ascontiguousarray(coeffs, dtype=np.float64)
+        n = c.shape[0]
+        assert c.shape == (n, 6, 3)
+        tr = np.ascontiguousarray(t_range, dtype=np.float64)
+        assert tr.shape == (2, n)
+        o, o_ptr = _opt_f64(origin, (3, n))
+        r, r_ptr = _opt_f64(rot, (9, n))
+        return n, (c, tr, o, r), (c.ctypes.data, tr.ctypes.data, o_ptr, r_ptr)      # (the arrays: alive while the pointers are used)
+
+    def paths(self, coeffs, t_range, origin=None, rot=None, n_samples=64, radius=0.116, max_dist=np.inf):
+        """n explicit paths sampled at n_samples times each: coeffs [n, 6, 3] (t^5 .. t^0 per axis), t_range [2, n], origin
+        [3, n] or None, rot [9, n] (row-major, planar) or None -> (records: PATH_CLEARANCE_DTYPE [n], n_colliding, kernel_ms).
+        radius defaults to the reference vehicle's 0.116 m."""
+        n, _arrays, ptrs = self._path_arrays(coeffs, t_range, origin, rot)
+        out = np.empty(n, PATH_CLEARANCE_DTYPE)
+        nc, ms = C.c_int64(0), C.c_float(0)
+        _status(library().afe_clearance_paths(self._h, n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(n_samples), float(radius), float(max_dist),
+                                              out.ctypes.data, C.byref(nc), C.byref(ms)))
+        return out, nc.value, ms.value
+
+    def paths_stats(self, coeffs, t_range, origin=None, rot=None, n_samples=64, radius=0.116, max_dist=np.inf):
+        """traversal counters of such a batch (counting build), summed over the samples: dict + kernel_ms"""
+        n, _arrays, ptrs = self._path_arrays(coeffs, t_range, origin, rot)
+        st = np.zeros(4, np.uint64)
+        ms = C.c_float(0)
+        _status(library().afe_clearance_paths_stats(self._h, n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(n_samples), float(radius),
+                                                    float(max_dist), st.ctypes.data, C.byref(ms)))
+        return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "samples"), (int(x) for x in st))), ms.value
+
+    def plans_engine(self, ensemble, plans, mount=None, first=0, count=None, n_samples=64, radius=0.116, max_dist=np.inf):
+        """The plans of vehicles [first, first+count) as rappids_plan returned them (a PlanOutput array or a PLAN_DTYPE
+        array, plans[i] for vehicle first + i), placed by each vehicle's pose on the device ->
+        (records: PATH_CLEARANCE_DTYPE [count], n_colliding, kernel_ms)."""
+        count = ensemble.n - first if count is None else count
+        if isinstance(plans, np.ndarray):
+            assert plans.dtype == PLAN_DTYPE
+            p = np.ascontiguousarray(plans)
+            assert p.size >= count
+            p_ptr = p.ctypes.data
+        else:
+            assert len(plans) >= count
+            p, p_ptr = plans, C.cast(plans, C.c_void_p)
+        m = None if mount is None else np.ascontiguousarray(mount, dtype=np.float64)
+        out = np.empty(max(count, 0), PATH_CLEARANCE_DTYPE)
+        nc, ms = C.c_int64(0), C.c_float(0)
+        _status(library().afe_clearance_plans_engine(ensemble.handle, self._h, int(first), int(count), None if m is None else m.ctypes.data,
+                                                     p_ptr, int(n_samples), float(radius), float(max_dist), out.ctypes.data,
+                                                     C.byref(nc), C.byref(ms)))
+        return out, nc.value, ms.value
 
 
 def clearance_check_hierarchy(triangles):

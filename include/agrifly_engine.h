@@ -476,6 +476,55 @@ int afe_clearance_query_stats(afe_clearance_map *m, int64_t n_points, const doub
 int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t count, double max_dist,
                                void *dist2_out, void *tri_out, void *closest_out, int out_is_device, float *kernel_ms);
 
+/* Path clearance: does a planned trajectory stay clear of the mesh?  A path is a quintic per axis, coeffs[6][3] =
+ * t^5 .. t^0 (the layout of afe_plan_output::coeffs), over a time range (t_begin, t_end), optionally placed by an
+ * origin o[3] and a row-major matrix R[9]: world point = o + R * p(t).  It is SAMPLED at n_samples = K times, 2 <= K <=
+ * 4096 (else AFE_ERR_OUT_OF_RANGE): t_k = t_begin + (t_end - t_begin) * (k / (K - 1)), t_{K-1} = t_end exactly; every
+ * sample is answered by the unbounded point query above and the K answers are reduced on the device to one record.
+ * csrc/afe_clearance.hip states every operation; tests/path_checker.py restates it.
+ *   n_nonfinite   samples with a non-finite coordinate (a NaN is data, not an error; such a sample is never a hit)
+ *   n_hit         samples with dist2 <= radius*radius;  k_first_hit the lowest such k (-1: none), tri_first_hit its
+ *                 triangle, t_first_hit its time (NaN: none)
+ *   min_dist2     the smallest dist2 among the samples with dist2 <= max_dist*max_dist;  k_min the lowest k among
+ *                 bitwise-equal minima;  tri_min, closest[3], t_min from that sample.  None: +inf, -1, -1, NaN, NaN.
+ * 0 < radius <= max_dist, radius finite, max_dist may be +inf (else AFE_ERR_INVALID_ARG).  max_dist only limits what is
+ * reported as the closest approach (and lets the search prune); the hit fields do not depend on it.
+ * What sampling does NOT cover: between two samples a path can come closer than at both.  The caller chooses K; for a
+ * spacing no larger than the radius, K >= 1 + path length / radius.  A continuous swept test is not provided. */
+typedef struct afe_path_clearance {      /* 8-byte members only, 96 bytes; the layout is ABI */
+  double  min_dist2, closest[3], t_min, t_first_hit;
+  int64_t k_min, tri_min, k_first_hit, tri_first_hit, n_hit, n_nonfinite;
+} afe_path_clearance;
+
+/* Pure host (no GPU): the sample times t_out[K] and world points xyz_out (planar [3][K]) of ONE path by the definition's
+ * expressions.  origin3 and rot9 may be NULL (rot9 without origin3: AFE_ERR_INVALID_ARG). */
+int afe_path_sample_points(const double *coeffs18, double t_begin, double t_end, const double *origin3,
+                           const double *rot9, int n_samples, double *t_out, double *xyz_out);
+
+/* n_paths explicit paths: coeffs [n][6][3]; t_range planar [2][n]; origin planar [3][n] or NULL; rot planar [9][n] or
+ * NULL (rot without origin: AFE_ERR_INVALID_ARG).  out: n_paths records.  n_colliding (optional): the number of paths
+ * with n_hit > 0, summed on the device.  n_paths == 0 is AFE_OK.  kernel_ms (optional): HIP-event time of the launch. */
+int afe_clearance_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range,
+                        const double *origin, const double *rot, int n_samples, double radius, double max_dist,
+                        afe_path_clearance *out, int64_t *n_colliding, float *kernel_ms);
+/* What the traversal did for such a batch (a counting build of the same kernel; the records are discarded), summed over
+ * the samples: stats[0] tree nodes visited, [1] triangle box tests, [2] double-precision closest-point evaluations,
+ * [3] samples (n_paths * n_samples). */
+int afe_clearance_paths_stats(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range,
+                              const double *origin, const double *rot, int n_samples, double radius, double max_dist,
+                              uint64_t stats[4], float *kernel_ms);
+
+/* The plans of vehicles [first, first+count) as afe_rappids_plan* returned them (camera frame): origin = the vehicle's
+ * position, rot = the camera-to-world matrix of att * mount (NULL mount: identity), both read on the device from the
+ * engine's slabs with the depth camera's arithmetic; the time range is [0, tf].  A plan with found == 0 is not sampled:
+ * its record is the empty one (+inf, every index -1, NaNs, both counts 0).  The plans are the only upload; the call is
+ * ordered on the engine's stream, a resident step grid ends first, engine and map must live on the same device.
+ * count == 0 with a valid range returns AFE_OK without touching the engine.  Calls on one map take turns. */
+int afe_clearance_plans_engine(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t count,
+                               const double mount[4], const afe_plan_output *plans, int n_samples,
+                               double radius, double max_dist, afe_path_clearance *out,
+                               int64_t *n_colliding, float *kernel_ms);
+
 /* Per-vehicle latches, device resident, for a closed loop that wants to know about contact without downloading
  * the state: 0 < contact_radius <= search_radius, both finite.  The monitor BORROWS engine and map: destroy it
  * before either of them (not tracked). */
