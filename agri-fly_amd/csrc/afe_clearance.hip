@@ -77,7 +77,7 @@
 //        min_dist2    = the smallest d2_k among the samples with d2_k < +inf and d2_k <= max_dist2;  k_min = the lowest k among bitwise-equal
 //                       minima;  tri_min, closest[3], t_min from that sample.  No such sample: +inf, -1, -1, NaN, NaN.
 //   afe_clearance_plans_engine: o = the vehicle's position, R = the camera-to-world matrix of att * mount, both formed with
-//   the arithmetic of afe_camera_pose_kernel (afe_render.hip; restated in path_pose below), the range is [0, tf]; a plan with
+//   the camera's own function (afe_pose.h, shared with afe_camera_pose_kernel), the range is [0, tf]; a plan with
 //   found == 0 is not sampled and gets the empty record (+inf, every index -1, NaNs, both counts 0).
 //
 // One wave per path, one sample per lane, batches of 64 samples; four paths per block, so the [32][256] stack carries over;
@@ -98,13 +98,14 @@
 #include <type_traits>
 #include <vector>
 
-#include "afe_render.h"   // afe::engine_device_view / afe::engine_stream_device
-
-namespace afe {
-void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);   // afe_engine.cpp: the engine's size, nothing touched
-}
+#include "afe_consumer.h"
+#include "afe_pose.h"
 
 namespace {
+
+using afe::DevBuf;
+using afe::EngineAccess;
+using afe::StreamTimer;
 
 constexpr int kBlock = 256;
 constexpr int kStack = 32;
@@ -440,38 +441,6 @@ __host__ __device__ __forceinline__ void path_sample(const double (&c)[18], doub
   }
 }
 
-// origin and camera-to-world matrix of vehicle v: the arithmetic of afe_camera_pose_kernel (afe_render.hip), operation for operation
-__device__ __forceinline__ void path_pose(const PathArgs &a, int64_t v, double (&o)[3], double (&R)[9]) {
-#pragma clang fp contract(off)
-  double p[3], q[4];
-  if (a.elem_size == 8) {
-    const double *P = (const double *)a.pos, *Q = (const double *)a.att;
-    for (int k = 0; k < 3; k++) p[k] = P[k * a.stride + v];
-    for (int k = 0; k < 4; k++) q[k] = Q[k * a.stride + v];
-  } else {
-    const float *P = (const float *)a.pos, *Q = (const float *)a.att;
-    for (int k = 0; k < 3; k++) p[k] = (double)P[k * a.stride + v];
-    for (int k = 0; k < 4; k++) q[k] = (double)Q[k * a.stride + v];
-  }
-  if (a.anchor_xy) { p[0] = a.anchor_xy[v] + p[0]; p[1] = a.anchor_xy[a.stride + v] + p[1]; }
-  const double *m = a.mount;
-  const double c0 = m[0] * q[0] - m[1] * q[1] - m[2] * q[2] - m[3] * q[3];
-  const double c1 = m[1] * q[0] + m[0] * q[1] + m[3] * q[2] - m[2] * q[3];
-  const double c2 = m[2] * q[0] - m[3] * q[1] + m[0] * q[2] + m[1] * q[3];
-  const double c3 = m[3] * q[0] + m[2] * q[1] - m[1] * q[2] + m[0] * q[3];
-  const double r0 = c0 * c0, r1 = c1 * c1, r2 = c2 * c2, r3 = c3 * c3;
-  o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-  R[0] = r0 + r1 - r2 - r3;
-  R[1] = 2 * c1 * c2 - 2 * c0 * c3;
-  R[2] = 2 * c1 * c3 + 2 * c0 * c2;
-  R[3] = 2 * c1 * c2 + 2 * c0 * c3;
-  R[4] = r0 - r1 + r2 - r3;
-  R[5] = 2 * c2 * c3 - 2 * c0 * c1;
-  R[6] = 2 * c1 * c3 - 2 * c0 * c2;
-  R[7] = 2 * c2 * c3 + 2 * c0 * c1;
-  R[8] = r0 - r1 - r2 + r3;
-}
-
 // smallest (d, l) of the wave in every lane; among equal d the lowest l.  Every lane of the wave takes part.
 __device__ __forceinline__ void wave_min_d2_lane(double &d, int &l) {
 #pragma unroll
@@ -533,7 +502,7 @@ __global__ void __launch_bounds__(kBlock) afe_path_clearance_kernel(PathArgs) { 
       for (int j = 0; j < 18; j++) c[j] = src[j];
       tb = 0.0; te = plan->tf;
       has_o = true; has_r = true;
-      path_pose(a, a.first + pi, o, R);
+      afe::camera_pose(a.pos, a.att, a.anchor_xy, a.stride, a.elem_size, a.mount, a.first + pi, o, R);
     } else {
       const double *src = a.coeffs + 18 * pi;
 #pragma unroll
@@ -749,24 +718,6 @@ bool mesh_ok(const float *triangles, int64_t n_tri) {
   return true;
 }
 
-int pick_gfx950(int device, int *out) {
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return AFE_ERR_NO_DEVICE;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return AFE_ERR_NO_DEVICE;
-  if (device >= n_dev) return AFE_ERR_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return AFE_ERR_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
-  *out = device;
-  return AFE_OK;
-}
-
-struct DevMem {
-  void *p = nullptr;
-  ~DevMem() { if (p) (void)hipFree(p); }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-};
-
 }  // namespace
 
 struct afe_clearance_map {
@@ -801,9 +752,8 @@ namespace {
 // launches the query for `count` points on `stream`, in runs below 2^31 threads
 template <bool MONITOR, bool COUNT>
 int launch_query(ClrArgs g, hipStream_t stream, float *kernel_ms) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernel_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) { if (e0) (void)hipEventDestroy(e0); return AFE_ERR_HIP; }
-  if (kernel_ms) (void)hipEventRecord(e0, stream);
+  StreamTimer timer(stream, kernel_ms != nullptr);
+  if (!timer.ok()) return AFE_ERR_HIP;
   int rc = AFE_OK;
   const int64_t total = g.count, first = g.first;
   double *d2 = g.dist2_out, *cl = g.closest_out;
@@ -818,13 +768,7 @@ int launch_query(ClrArgs g, hipStream_t stream, float *kernel_ms) {
     hipLaunchKernelGGL((afe_clearance_kernel<MONITOR, COUNT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, g);
     rc = hipGetLastError() == hipSuccess ? AFE_OK : AFE_ERR_HIP;
   }
-  if (kernel_ms) {
-    (void)hipEventRecord(e1, stream);
-    if (rc == AFE_OK && hipEventSynchronize(e1) != hipSuccess) rc = AFE_ERR_HIP;
-    if (rc == AFE_OK) (void)hipEventElapsedTime(kernel_ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
-  return rc;
+  return timer.finish(rc, kernel_ms);
 }
 
 bool radius_ok(double max_dist) { return max_dist > 0.0; }   // false for NaN, 0, negatives; +inf passes
@@ -833,12 +777,11 @@ int query_points(afe_clearance_map *m, int64_t n_points, const double *pos, doub
                  double *closest_out, float *kernel_ms, uint64_t *stats) {
   if (hipSetDevice(m->device) != hipSuccess) return AFE_ERR_HIP;
   const size_t n = (size_t)n_points;
-  DevMem d_pos, d_d2, d_tri, d_cl, d_stats;
-  if (!d_pos.alloc(n * 24) || !d_d2.alloc(n * 8) || !d_tri.alloc(n * 4) || (closest_out && !d_cl.alloc(n * 24)) || (stats && !d_stats.alloc(24))) {
+  DevBuf d_pos, d_d2, d_tri, d_cl, d_stats;
+  if (!d_pos.upload(pos, n * 24) || !d_d2.alloc(n * 8) || !d_tri.alloc(n * 4) || (closest_out && !d_cl.alloc(n * 24)) || (stats && !d_stats.alloc(24))) {
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
-  if (hipMemcpy(d_pos.p, pos, n * 24, hipMemcpyHostToDevice) != hipSuccess) return AFE_ERR_HIP;
   if (stats && hipMemset(d_stats.p, 0, 24) != hipSuccess) return AFE_ERR_HIP;
   ClrArgs g = m->base;
   g.max_dist2 = max_dist * max_dist;
@@ -849,12 +792,10 @@ int query_points(afe_clearance_map *m, int64_t n_points, const double *pos, doub
   const int rc = stats ? launch_query<false, true>(g, nullptr, &ms) : launch_query<false, false>(g, nullptr, &ms);
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
-  if (hipMemcpy(dist2_out, d_d2.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tri_out, d_tri.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      (closest_out && hipMemcpy(closest_out, d_cl.p, n * 24, hipMemcpyDeviceToHost) != hipSuccess))
-    return AFE_ERR_HIP;
+  if (!d_d2.download(dist2_out, n * 8) || !d_tri.download(tri_out, n * 4) || (closest_out && !d_cl.download(closest_out, n * 24))) return AFE_ERR_HIP;
   if (stats) {
     unsigned long long host[3];
-    if (hipMemcpy(host, d_stats.p, 24, hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
+    if (!d_stats.download(host, 24)) return AFE_ERR_HIP;
     for (int k = 0; k < 3; k++) stats[k] = host[k];
     stats[3] = (uint64_t)n_points;
   }
@@ -866,7 +807,7 @@ int query_points(afe_clearance_map *m, int64_t n_points, const double *pos, doub
 extern "C" int afe_clearance_map_create(int device, const float *triangles, int64_t n_tri, afe_clearance_map **out) {
   if (!out || !mesh_ok(triangles, n_tri)) return AFE_ERR_INVALID_ARG;
   int dev = 0;
-  int rc = pick_gfx950(device, &dev);
+  int rc = afe::pick_gfx950(device, &dev);
   if (rc != AFE_OK) return rc;
   HostMap h;
   rc = h.build(triangles, n_tri);
@@ -952,24 +893,15 @@ extern "C" int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, i
                                           void *tri_out, void *closest_out, int out_is_device, float *kernel_ms) {
   if (!e || !m || first < 0 || count < 0 || !radius_ok(max_dist)) return AFE_ERR_INVALID_ARG;
   if (count > 0 && (!dist2_out || !tri_out)) return AFE_ERR_INVALID_ARG;
-  {
-    int64_t first_global = 0, n = 0;
-    afe::engine_shard(e, &first_global, &n);
-    if (first > n || count > n - first) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
-    if (count == 0) return AFE_OK;          // a valid range of nothing: answered before the engine is touched
-  }
-  hipStream_t stream = nullptr;
-  int device = 0;
-  afe::engine_stream_device(e, (void **)&stream, &device);     // (ends a resident grid, as the camera does)
-  if (device != m->device) return AFE_ERR_INVALID_ARG;
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  int rc = afe::engine_device_view(e, &view);
+  if (afe::engine_range_bad(e, first, count)) return AFE_ERR_OUT_OF_RANGE;
+  if (count == 0) return AFE_OK;          // a valid range of nothing: answered before the engine is touched
+  EngineAccess acc;
+  int rc = afe::engine_enter(e, &acc);     // (ends a resident grid, as the camera does)
   if (rc != AFE_OK) return rc;
-  if (first > view.n_vehicles || count > view.n_vehicles - first) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  if (acc.device != m->device) return AFE_ERR_INVALID_ARG;
+  const afe_device_view &view = acc.view;
   const size_t n = (size_t)count;
-  DevMem d_d2, d_tri, d_cl;
+  DevBuf d_d2, d_tri, d_cl;
   ClrArgs g = m->base;
   g.max_dist2 = max_dist * max_dist;
   g.pos = view.pos; g.anchor_xy = view.pos_anchor_xy; g.stride = view.stride; g.first = first; g.count = count; g.elem_size = view.state_elem_size;
@@ -981,12 +913,10 @@ extern "C" int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, i
     g.dist2_out = (double *)d_d2.p; g.tri_out = (int32_t *)d_tri.p; g.closest_out = (double *)d_cl.p;
   }
   float ms = 0;
-  rc = launch_query<false, false>(g, stream, &ms);     // synchronises (timing)
+  rc = launch_query<false, false>(g, acc.stream, &ms);     // synchronises (timing)
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
-  if (!out_is_device &&
-      (hipMemcpy(dist2_out, d_d2.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tri_out, d_tri.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-       (closest_out && hipMemcpy(closest_out, d_cl.p, n * 24, hipMemcpyDeviceToHost) != hipSuccess)))
+  if (!out_is_device && (!d_d2.download(dist2_out, n * 8) || !d_tri.download(tri_out, n * 4) || (closest_out && !d_cl.download(closest_out, n * 24))))
     return AFE_ERR_HIP;
   return AFE_OK;
 }
@@ -1002,9 +932,8 @@ bool path_samples_ok(int n_samples) { return n_samples >= kMinSamples && n_sampl
 // one launch on `stream`; with kernel_ms, waits for it
 template <bool ENGINE>
 int launch_paths(const PathArgs &a, hipStream_t stream, float *kernel_ms) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernel_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) { if (e0) (void)hipEventDestroy(e0); return AFE_ERR_HIP; }
-  if (kernel_ms) (void)hipEventRecord(e0, stream);
+  StreamTimer timer(stream, kernel_ms != nullptr);
+  if (!timer.ok()) return AFE_ERR_HIP;
   const dim3 grid((unsigned)((a.n_paths + kPathsPerBlock - 1) / kPathsPerBlock)), block(kBlock);
   // path_args() reads the argument segment from offset 0: the kernel takes PathArgs by value and nothing else
   static_assert(std::is_same<decltype(&afe_path_clearance_kernel<ENGINE, false>), void (*)(PathArgs)>::value, "one by-value PathArgs");
@@ -1012,14 +941,7 @@ int launch_paths(const PathArgs &a, hipStream_t stream, float *kernel_ms) {
   if constexpr (!ENGINE) counting = a.stats != nullptr;        // (the counting build serves explicit paths only)
   if constexpr (!ENGINE) { if (counting) hipLaunchKernelGGL((afe_path_clearance_kernel<false, true>), grid, block, 0, stream, a); }
   if (!counting) hipLaunchKernelGGL((afe_path_clearance_kernel<ENGINE, false>), grid, block, 0, stream, a);
-  int rc = hipGetLastError() == hipSuccess ? AFE_OK : AFE_ERR_HIP;
-  if (kernel_ms) {
-    (void)hipEventRecord(e1, stream);
-    if (rc == AFE_OK && hipEventSynchronize(e1) != hipSuccess) rc = AFE_ERR_HIP;
-    if (rc == AFE_OK) (void)hipEventElapsedTime(kernel_ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
-  return rc;
+  return timer.finish(hipGetLastError() == hipSuccess ? AFE_OK : AFE_ERR_HIP, kernel_ms);
 }
 
 int paths_args_check(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range, const double *origin, const double *rot,
@@ -1035,16 +957,12 @@ int run_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const
               int n_samples, double radius, double max_dist, afe_path_clearance *out, int64_t *n_colliding, float *kernel_ms, uint64_t *stats) {
   if (hipSetDevice(m->device) != hipSuccess) return AFE_ERR_HIP;
   const size_t n = (size_t)n_paths;
-  DevMem d_c, d_t, d_o, d_r, d_out, d_words;
-  if (!d_c.alloc(n * 144) || !d_t.alloc(n * 16) || (origin && !d_o.alloc(n * 24)) || (rot && !d_r.alloc(n * 72)) || !d_out.alloc(n * sizeof(afe_path_clearance)) ||
-      !d_words.alloc(32)) {
+  DevBuf d_c, d_t, d_o, d_r, d_out, d_words;
+  if (!d_c.upload(coeffs, n * 144) || !d_t.upload(t_range, n * 16) || (origin && !d_o.upload(origin, n * 24)) || (rot && !d_r.upload(rot, n * 72)) ||
+      !d_out.alloc(n * sizeof(afe_path_clearance)) || !d_words.alloc(32) || hipMemset(d_words.p, 0, 32) != hipSuccess) {
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
-  if (hipMemcpy(d_c.p, coeffs, n * 144, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_t.p, t_range, n * 16, hipMemcpyHostToDevice) != hipSuccess ||
-      (origin && hipMemcpy(d_o.p, origin, n * 24, hipMemcpyHostToDevice) != hipSuccess) ||
-      (rot && hipMemcpy(d_r.p, rot, n * 72, hipMemcpyHostToDevice) != hipSuccess) || hipMemset(d_words.p, 0, 32) != hipSuccess)
-    return AFE_ERR_HIP;
   PathArgs a;
   std::memset(&a, 0, sizeof(a));
   a.t = m->base;
@@ -1059,9 +977,7 @@ int run_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
   unsigned long long words[4];
-  if ((out && hipMemcpy(out, d_out.p, n * sizeof(afe_path_clearance), hipMemcpyDeviceToHost) != hipSuccess) ||
-      hipMemcpy(words, d_words.p, 32, hipMemcpyDeviceToHost) != hipSuccess)
-    return AFE_ERR_HIP;
+  if ((out && !d_out.download(out, n * sizeof(afe_path_clearance))) || !d_words.download(words, 32)) return AFE_ERR_HIP;
   if (n_colliding) *n_colliding = (int64_t)words[0];
   if (stats) {
     for (int k = 0; k < 3; k++) stats[k] = words[1 + k];
@@ -1110,22 +1026,14 @@ extern "C" int afe_clearance_plans_engine(afe_engine *e, afe_clearance_map *m, i
   if (!e || !m || first < 0 || count < 0 || !path_radii_ok(radius, max_dist)) return AFE_ERR_INVALID_ARG;
   if (count > 0 && (!plans || !out)) return AFE_ERR_INVALID_ARG;
   if (!path_samples_ok(n_samples)) return AFE_ERR_OUT_OF_RANGE;
-  {
-    int64_t first_global = 0, n = 0;
-    afe::engine_shard(e, &first_global, &n);
-    if (first > n || count > n - first || count > kMaxPaths) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
-    if (count == 0) { if (n_colliding) *n_colliding = 0; return AFE_OK; }   // a valid range of nothing: answered before the engine is touched
-  }
-  hipStream_t stream = nullptr;
-  int device = 0;
-  afe::engine_stream_device(e, (void **)&stream, &device);     // (ends a resident grid, as the camera does)
-  if (device != m->device) return AFE_ERR_INVALID_ARG;
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  int rc = afe::engine_device_view(e, &view);
+  if (afe::engine_range_bad(e, first, count) || count > kMaxPaths) return AFE_ERR_OUT_OF_RANGE;
+  if (count == 0) { if (n_colliding) *n_colliding = 0; return AFE_OK; }   // a valid range of nothing: answered before the engine is touched
+  EngineAccess acc;
+  int rc = afe::engine_enter(e, &acc);     // (ends a resident grid, as the camera does)
   if (rc != AFE_OK) return rc;
-  if (first > view.n_vehicles || count > view.n_vehicles - first) return AFE_ERR_OUT_OF_RANGE;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  if (acc.device != m->device) return AFE_ERR_INVALID_ARG;
+  const afe_device_view &view = acc.view;
+  const hipStream_t stream = acc.stream;
   const size_t n = (size_t)count, plan_bytes = n * sizeof(afe_plan_output), rec_bytes = n * sizeof(afe_path_clearance);
   std::lock_guard<std::mutex> turn(m->scratch_lock);
   if (m->scratch_bytes < plan_bytes + rec_bytes + 8) {
@@ -1185,17 +1093,12 @@ extern "C" int afe_contact_monitor_create(afe_engine *e, afe_clearance_map *m, d
                                           afe_contact_monitor **out) {
   if (!e || !m || !out) return AFE_ERR_INVALID_ARG;
   if (!(contact_radius > 0.0) || !(contact_radius <= search_radius) || !std::isfinite(search_radius)) return AFE_ERR_INVALID_ARG;
-  hipStream_t stream = nullptr;
-  int device = 0;
-  afe::engine_stream_device(e, (void **)&stream, &device);
-  if (device != m->device) return AFE_ERR_INVALID_ARG;
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  int rc = afe::engine_device_view(e, &view);
+  EngineAccess acc;
+  int rc = afe::engine_enter(e, &acc);
   if (rc != AFE_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  if (acc.device != m->device) return AFE_ERR_INVALID_ARG;
   afe_contact_monitor *c = new afe_contact_monitor();
-  c->engine = e; c->map = m; c->n = view.n_vehicles; c->device = device;
+  c->engine = e; c->map = m; c->n = acc.view.n_vehicles; c->device = acc.device;
   c->contact2 = contact_radius * contact_radius;
   c->search2 = search_radius * search_radius;
   const size_t n = (size_t)c->n;
@@ -1206,8 +1109,8 @@ extern "C" int afe_contact_monitor_create(afe_engine *e, afe_clearance_map *m, d
     (void)afe_contact_monitor_destroy(c);
     return AFE_ERR_HIP;
   }
-  rc = monitor_reset_range(c, 0, c->n, stream);
-  if (rc == AFE_OK && hipStreamSynchronize(stream) != hipSuccess) rc = AFE_ERR_HIP;
+  rc = monitor_reset_range(c, 0, c->n, acc.stream);
+  if (rc == AFE_OK && hipStreamSynchronize(acc.stream) != hipSuccess) rc = AFE_ERR_HIP;
   if (rc != AFE_OK) { (void)afe_contact_monitor_destroy(c); return rc; }
   *out = c;
   return AFE_OK;
@@ -1215,18 +1118,15 @@ extern "C" int afe_contact_monitor_create(afe_engine *e, afe_clearance_map *m, d
 
 extern "C" int afe_contact_monitor_update(afe_contact_monitor *c, int64_t *n_in_contact, int64_t *n_ever_in_contact) {
   if (!c) return AFE_ERR_INVALID_ARG;
-  hipStream_t stream = nullptr;
-  int device = 0;
-  afe::engine_stream_device(c->engine, (void **)&stream, &device);
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  int rc = afe::engine_device_view(c->engine, &view);
+  EngineAccess acc;
+  int rc = afe::engine_enter(c->engine, &acc);
   if (rc != AFE_OK) return rc;
+  const afe_device_view &view = acc.view;
+  const hipStream_t stream = acc.stream;
   if (view.n_vehicles != c->n) return AFE_ERR_INVALID_ARG;
   uint64_t now_us = 0;
   rc = afe_time_us(c->engine, &now_us);
   if (rc != AFE_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
   ClrArgs g = c->map->base;
   g.max_dist2 = c->search2;
   g.pos = view.pos; g.anchor_xy = view.pos_anchor_xy; g.stride = view.stride; g.first = 0; g.count = c->n; g.elem_size = view.state_elem_size;

@@ -22,12 +22,11 @@
 #include <vector>
 
 #include "afe_host.h"
-#include "afe_render.h"   // engine_stream_device
+#include "afe_consumer.h"   // engine_stream_device, engine_shard
 
 namespace afe {
 // afe_engine.cpp
 int engine_pack_to_scratch(afe_engine *e, float **scratch);   // positions -> planar fp32 [3][n] scratch, on the engine's stream
-void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);
 }  // namespace afe
 using namespace afe;
 

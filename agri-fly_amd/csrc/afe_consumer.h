@@ -1,0 +1,110 @@
+// afe_consumer.h -- host plumbing shared by the library's consumers of the engine's device state and by the perception
+// entry points: depth camera (afe_render.hip), planner API (afe_planner_api.cpp), clearance query, contact monitor and path
+// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip).  Internal to the library, host only, header only.
+//
+//   engine_stream_device / engine_device_view / engine_shard   the engine's entry points for the library's other translation
+//                        units (implemented in afe_engine.cpp; afe_world.hip and afe_comm.cpp use the first and the last alone)
+//   pick_gfx950          the device a create call runs on: the given one or the current one, refused unless it is a gfx950
+//   DevBuf               a device allocation that lives as long as its scope
+//   StreamTimer          two events round the launches of a call; without timing it is nothing and synchronises nothing
+//   engine_enter         the ONE way a consumer gets at the engine: stream, device and view, the device made current
+//   engine_range_bad     [first, first + count) against the engine's size, nothing touched
+//
+// ORDER OF REFUSALS at an entry that consumes an engine.  First the call's own arguments (AFE_ERR_INVALID_ARG, then
+// AFE_ERR_OUT_OF_RANGE), then the range against the engine's size (engine_range_bad) and the empty request -- answered
+// AFE_OK before the engine is touched, so an audit of nothing does not end a resident grid -- then engine_enter: it passes
+// the engine's gate (a resident grid ends here, a failed engine refuses with the status of its first failure), then
+// hipSetDevice (AFE_ERR_HIP).  Only THEN the consumer compares its own handle with what it got (a map or scene on another
+// device, a monitor made for another vehicle count: AFE_ERR_INVALID_ARG).  So a call that is wrong in two ways at once -- a
+// failed engine AND a handle on another device -- reports the engine.  afe_render_depth_engine alone takes the range from
+// the view and therefore enters first: engine, range, empty request, device.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+
+#include "../../include/agrifly_engine.h"
+
+namespace afe {
+
+// implemented in afe_engine.cpp: the stream the engine launches on and its device
+void engine_stream_device(afe_engine *e, void **stream, int *device);
+// afe_get_device_view for the library's own consumers (the slabs do not leave the engine: afe_sync keeps its short form)
+int engine_device_view(afe_engine *e, struct afe_device_view *out);
+// afe_engine.cpp: the engine's size, nothing touched
+void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);
+
+inline int pick_gfx950(int device, int *out) {
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return AFE_ERR_NO_DEVICE;
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return AFE_ERR_NO_DEVICE;
+  if (device >= n_dev) return AFE_ERR_NO_DEVICE;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return AFE_ERR_NO_DEVICE;
+  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  *out = device;
+  return AFE_OK;
+}
+
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+  bool upload(const void *src, size_t bytes) { return alloc(bytes) && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
+  bool download(void *host, size_t bytes) const { return hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+};
+
+// The start event is recorded on construction; finish() goes behind the last launch.  Untimed: no event, no record, no wait.
+struct StreamTimer {
+  hipStream_t stream;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool timed;
+  StreamTimer(hipStream_t stream_, bool timed_) : stream(stream_), timed(timed_) {
+    if (timed && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, stream);
+  }
+  StreamTimer(const StreamTimer &) = delete;
+  StreamTimer &operator=(const StreamTimer &) = delete;
+  ~StreamTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  bool ok() const { return !timed || e1 != nullptr; }      // false: an event could not be made -- launch nothing, AFE_ERR_HIP
+  // the launches' status in, the call's status out; waits for the launches only if they went out, then *ms = their time
+  int finish(int status, float *ms) {
+    if (!timed) return status;
+    if (!ok()) return AFE_ERR_HIP;
+    (void)hipEventRecord(e1, stream);
+    if (status == AFE_OK && hipEventSynchronize(e1) != hipSuccess) status = AFE_ERR_HIP;
+    if (status == AFE_OK) (void)hipEventElapsedTime(ms, e0, e1);
+    return status;
+  }
+};
+
+struct EngineAccess {
+  hipStream_t stream;
+  int device;
+  afe_device_view view;
+};
+
+// (see ORDER OF REFUSALS above)
+inline int engine_enter(afe_engine *e, EngineAccess *a) {
+  a->stream = nullptr;
+  a->device = 0;
+  engine_stream_device(e, (void **)&a->stream, &a->device);
+  a->view.struct_bytes = sizeof(a->view);
+  const int rc = engine_device_view(e, &a->view);
+  if (rc != AFE_OK) return rc;
+  return hipSetDevice(a->device) == hipSuccess ? AFE_OK : AFE_ERR_HIP;
+}
+
+inline bool engine_range_bad(const afe_engine *e, int64_t first, int64_t count) {
+  int64_t first_global = 0, n = 0;
+  engine_shard(e, &first_global, &n);
+  return first > n || count > n - first;   // (no sum: it can wrap)
+}
+
+}  // namespace afe

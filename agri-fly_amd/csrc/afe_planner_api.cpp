@@ -7,8 +7,9 @@
 #include <random>
 #include <vector>
 
-#include "afe_planner.h"
+#include "afe_consumer.h"
 #include "afe_host.h"   // afe_dev_env
+#include "afe_planner.h"
 
 using namespace afe;
 
@@ -76,10 +77,10 @@ void release_scratch_locked() {
   g_scratch_device = -1;
 }
 
-struct DevBuf {
+struct PooledBuf {
   void *p = nullptr;
   int slot;
-  explicit DevBuf(int slot_) : slot(slot_) {}
+  explicit PooledBuf(int slot_) : slot(slot_) {}
   bool alloc(size_t bytes) {
     ScratchSlot &s = g_scratch[slot];
     if (bytes == 0) bytes = 1;
@@ -139,19 +140,13 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
     for (int64_t i = 0; i < n; i++) if (image_index[i] < 0 || image_index[i] >= n_images) return AFE_ERR_OUT_OF_RANGE;
   if (sample_table)
     for (int64_t i = 0; i < n; i++) if (sample_table[i] < 0 || sample_table[i] >= n_tables) return AFE_ERR_OUT_OF_RANGE;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return AFE_ERR_NO_DEVICE;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return AFE_ERR_NO_DEVICE;
-  if (device >= n_dev) return AFE_ERR_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return AFE_ERR_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  const int prc = pick_gfx950(device, &device);
+  if (prc != AFE_OK) return prc;
 
   std::lock_guard<std::mutex> scratch_lock(g_scratch_mutex);
   if (g_scratch_device != device) { release_scratch_locked(); (void)hipSetDevice(device); g_scratch_device = device; }
   const size_t px = (size_t)cfg->width * cfg->height;
-  DevBuf d_img(0), d_imgT(1), d_cc(2), d_cb(3), d_cs(4), d_idx(5), d_v(6), d_a(7), d_g(8), d_c(9), d_s(10), d_t(11), d_pyr(12), d_out(13),
+  PooledBuf d_img(0), d_imgT(1), d_cc(2), d_cb(3), d_cs(4), d_idx(5), d_v(6), d_a(7), d_g(8), d_c(9), d_s(10), d_t(11), d_pyr(12), d_out(13),
       d_flags(14), d_resume(15), d_bins(16), d_sums(17), d_order(18);
   if ((!depth_on_device && !d_img.upload(depth_images, (size_t)n_images * px * 2)) || !d_v.upload(vel0, (size_t)n * 24) ||
       !d_a.upload(acc0, (size_t)n * 24) || !d_g.upload(grav, (size_t)n * 24) ||
@@ -200,16 +195,10 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
   b.bin_list = (int32_t *)d_bins.p + 64;
   b.ordered = 0;
 
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return AFE_ERR_HIP;
-  (void)hipEventRecord(e0, 0);
-  const int lrc = launch_rappids(*cfg, b, nullptr);
-  (void)hipEventRecord(e1, 0);
-  int rc = AFE_OK;
-  if (lrc != 0 || hipEventSynchronize(e1) != hipSuccess) rc = AFE_ERR_HIP;
+  StreamTimer timer(nullptr, true);
+  if (!timer.ok()) return AFE_ERR_HIP;
   float ms = 0;
-  if (rc == AFE_OK) (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  const int rc = timer.finish(launch_rappids(*cfg, b, nullptr) == 0 ? AFE_OK : AFE_ERR_HIP, &ms);
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
   if (hipMemcpy(out, d_out.p, (size_t)n * sizeof(PlanOutput), hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;

@@ -31,8 +31,10 @@
 #include <mutex>
 #include <vector>
 
-#include "afe_render.h"
+#include "afe_consumer.h"
 #include "afe_host.h"   // afe_dev_env
+#include "afe_pose.h"
+#include "afe_render.h"
 
 namespace afe {
 
@@ -278,37 +280,8 @@ __global__ void afe_camera_pose_kernel(PoseArgs a) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.count) return;
-  const int64_t v = a.first + i;
-  double p[3], q[4];
-  if (a.elem_size == 8) {
-    const double *P = (const double *)a.pos, *Q = (const double *)a.att;
-    for (int k = 0; k < 3; k++) p[k] = P[k * a.stride + v];
-    for (int k = 0; k < 4; k++) q[k] = Q[k * a.stride + v];
-  } else {
-    const float *P = (const float *)a.pos, *Q = (const float *)a.att;
-    for (int k = 0; k < 3; k++) p[k] = (double)P[k * a.stride + v];
-    for (int k = 0; k < 4; k++) q[k] = (double)Q[k * a.stride + v];
-  }
-  if (a.anchor_xy) { p[0] = a.anchor_xy[v] + p[0]; p[1] = a.anchor_xy[a.stride + v] + p[1]; }
-  const double *m = a.mount;
-  // att * mount, Rotation.hpp:124-131
-  const double c0 = m[0] * q[0] - m[1] * q[1] - m[2] * q[2] - m[3] * q[3];
-  const double c1 = m[1] * q[0] + m[0] * q[1] + m[3] * q[2] - m[2] * q[3];
-  const double c2 = m[2] * q[0] - m[3] * q[1] + m[0] * q[2] + m[1] * q[3];
-  const double c3 = m[3] * q[0] + m[2] * q[1] - m[1] * q[2] + m[0] * q[3];
-  const double r0 = c0 * c0, r1 = c1 * c1, r2 = c2 * c2, r3 = c3 * c3;
   double *o = a.poses + 12 * i;
-  o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-  // Rotation.hpp:196-220
-  o[3] = r0 + r1 - r2 - r3;
-  o[4] = 2 * c1 * c2 - 2 * c0 * c3;
-  o[5] = 2 * c1 * c3 + 2 * c0 * c2;
-  o[6] = 2 * c1 * c2 + 2 * c0 * c3;
-  o[7] = r0 - r1 + r2 - r3;
-  o[8] = 2 * c2 * c3 - 2 * c0 * c1;
-  o[9] = 2 * c1 * c3 - 2 * c0 * c2;
-  o[10] = 2 * c2 * c3 + 2 * c0 * c1;
-  o[11] = r0 - r1 - r2 + r3;
+  camera_pose(a.pos, a.att, a.anchor_xy, a.stride, a.elem_size, a.mount, a.first + i, o, o + 3);
 }
 
 // One triangle as the kernel wants it (96 B, fetched by scalar loads -- the leaf being visited is the
@@ -827,28 +800,6 @@ struct afe_scene {
 };
 
 namespace {
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-  bool upload(const void *src, size_t bytes) {
-    return alloc(bytes) && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  }
-};
-
-int pick_device(int device, int *out) {
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return AFE_ERR_NO_DEVICE;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return AFE_ERR_NO_DEVICE;
-  if (device >= n_dev) return AFE_ERR_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return AFE_ERR_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
-  *out = device;
-  return AFE_OK;
-}
-
 bool camera_ok(const afe_camera *c) {
   return c && c->width > 0 && c->height > 0 && c->focal_length > 0 && c->depth_scale > 0 && c->max_count > 0 &&
          c->max_count <= 65535;
@@ -891,9 +842,8 @@ int launch_render(afe_scene *s, const afe_camera *cam, int64_t count, const doub
   if (r.tiles_per_view > max_blocks) return AFE_ERR_OUT_OF_RANGE;
   const int64_t views_per_launch = max_blocks / r.tiles_per_view;
   const size_t px = (size_t)cam->width * cam->height;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernel_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) return AFE_ERR_HIP;
-  if (kernel_ms) (void)hipEventRecord(e0, stream);
+  StreamTimer timer(stream, kernel_ms != nullptr);
+  if (!timer.ok()) return AFE_ERR_HIP;
   int rc = AFE_OK;
   for (int64_t v0 = 0; v0 < count && rc == AFE_OK; v0 += views_per_launch) {
     const int64_t nv = (count - v0) < views_per_launch ? (count - v0) : views_per_launch;
@@ -943,13 +893,7 @@ int launch_render(afe_scene *s, const afe_camera *cam, int64_t count, const doub
       table->taken = false;
     }
   }
-  if (kernel_ms) {
-    (void)hipEventRecord(e1, stream);
-    if (rc == AFE_OK && hipEventSynchronize(e1) != hipSuccess) rc = AFE_ERR_HIP;
-    if (rc == AFE_OK) (void)hipEventElapsedTime(kernel_ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
-  return rc;
+  return timer.finish(rc, kernel_ms);
 }
 
 int launch_poses(const void *pos, const double *anchor_xy, const void *att, int64_t stride, int64_t first, int64_t count, int elem_size,
@@ -994,7 +938,7 @@ extern "C" int afe_scene_create(int device, const float *triangles, int64_t n_tr
   if (!triangles || n_tri <= 0 || n_tri > 0x3fffffff || !out) return AFE_ERR_INVALID_ARG;
   for (int64_t i = 0; i < 9 * n_tri; i++) if (!std::isfinite(triangles[i])) return AFE_ERR_INVALID_ARG;
   int dev = 0;
-  const int rc = pick_device(device, &dev);
+  const int rc = pick_gfx950(device, &dev);
   if (rc != AFE_OK) return rc;
 
   // Triangles whose own box is a good part of the scene's (a ground plane's two) stay out of the tree: inside it they
@@ -1231,7 +1175,7 @@ extern "C" int afe_render_depth(afe_scene *s, const afe_camera *cam, int64_t n_v
   rc = launch_render(s, cam, n_views, (const double *)d_pose.p, (uint16_t *)d_out.p, nullptr, &ms);
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
-  if (hipMemcpy(depth_out, d_out.p, (size_t)n_views * px * 2, hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
+  if (!d_out.download(depth_out, (size_t)n_views * px * 2)) return AFE_ERR_HIP;
   return AFE_OK;
 }
 
@@ -1257,7 +1201,7 @@ extern "C" int afe_render_depth_stats(afe_scene *s, const afe_camera *cam, int64
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
   unsigned long long host[8];
-  if (hipMemcpy(host, d_cnt.p, 64, hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
+  if (!d_cnt.download(host, 64)) return AFE_ERR_HIP;
   for (int k = 0; k < 8; k++) stats[k] = host[k];
   return AFE_OK;
 }
@@ -1266,17 +1210,14 @@ extern "C" int afe_render_depth_engine(afe_engine *e, afe_scene *s, const afe_ca
                                        int64_t count, const double mount[4], void *depth_out, int out_is_device,
                                        float *kernel_ms) {
   if (!e || !s || !camera_ok(cam) || count < 0 || first < 0 || !depth_out) return AFE_ERR_INVALID_ARG;
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  int rc = engine_device_view(e, &view);
+  EngineAccess a;
+  int rc = engine_enter(e, &a);
   if (rc != AFE_OK) return rc;
+  const afe_device_view &view = a.view;
   if (first > view.n_vehicles || count > view.n_vehicles - first) return AFE_ERR_OUT_OF_RANGE;   // (no sum: it can wrap)
   if (count == 0) return AFE_OK;
-  hipStream_t stream = nullptr;
-  int device = 0;
-  engine_stream_device(e, (void **)&stream, &device);
-  if (device != s->device) return AFE_ERR_INVALID_ARG;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  if (a.device != s->device) return AFE_ERR_INVALID_ARG;
+  hipStream_t stream = a.stream;
   const size_t px = (size_t)cam->width * cam->height;
   DevBuf d_pose, d_out;
   if (!d_pose.alloc((size_t)count * 96)) return AFE_ERR_HIP;
@@ -1300,7 +1241,7 @@ extern "C" int afe_render_depth_engine(afe_engine *e, afe_scene *s, const afe_ca
 extern "C" int afe_device_alloc(int device, uint64_t bytes, void **out) {
   if (!out || bytes == 0) return AFE_ERR_INVALID_ARG;
   int dev = 0;
-  const int rc = pick_device(device, &dev);
+  const int rc = pick_gfx950(device, &dev);
   if (rc != AFE_OK) return rc;
   return hipMalloc(out, bytes) == hipSuccess ? AFE_OK : AFE_ERR_HIP;
 }

@@ -64,11 +64,7 @@
 #include <limits>
 #include <vector>
 
-#include "afe_render.h"   // afe::engine_device_view / afe::engine_stream_device
-
-namespace afe {
-void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);   // afe_engine.cpp: the engine's size, nothing touched
-}
+#include "afe_consumer.h"
 
 static_assert(sizeof(afe_group_stats) == 23 * 8, "afe_group_stats: 8-byte members only, the layout is ABI");
 
@@ -415,14 +411,12 @@ size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 // engine access for one call: stream, device and view (passes the engine's entry gate: a resident grid ends, a failed
 // engine refuses by naming its first failure)
 int enter(afe_stats_monitor *m, hipStream_t *stream, StatsArgs *g, int *elem) {
-  int device = 0;
-  afe::engine_stream_device(m->engine, (void **)stream, &device);
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  const int rc = afe::engine_device_view(m->engine, &view);
+  afe::EngineAccess acc;
+  const int rc = afe::engine_enter(m->engine, &acc);
   if (rc != AFE_OK) return rc;
-  if (view.n_vehicles != m->n || device != m->device) return AFE_ERR_INVALID_ARG;
-  if (hipSetDevice(device) != hipSuccess) return AFE_ERR_HIP;
+  const afe_device_view &view = acc.view;
+  if (view.n_vehicles != m->n || acc.device != m->device) return AFE_ERR_INVALID_ARG;
+  *stream = acc.stream;
   *g = m->args;
   g->pos = view.pos; g->vel = view.vel; g->att = view.att; g->ang_vel = view.ang_vel;
   g->anchor_xy = view.pos_anchor_xy; g->stride = view.stride;
@@ -478,14 +472,13 @@ extern "C" int afe_stats_create(afe_engine *e, const int64_t *edges, int n_group
   if (rc != AFE_OK) return rc;
   afe_stats_monitor *m = new afe_stats_monitor();
   m->engine = e; m->n = n; m->n_groups = n_groups; m->n_chunks = L.n_chunks;
-  hipStream_t stream = nullptr;
-  afe::engine_stream_device(e, (void **)&stream, &m->device);
-  afe_device_view view;
-  view.struct_bytes = sizeof(view);
-  rc = afe::engine_device_view(e, &view);
-  if (rc == AFE_OK && view.n_vehicles != n) rc = AFE_ERR_INVALID_ARG;
-  if (rc == AFE_OK && hipSetDevice(m->device) != hipSuccess) rc = AFE_ERR_HIP;
+  afe::EngineAccess acc;
+  rc = afe::engine_enter(e, &acc);
+  if (rc == AFE_OK && acc.view.n_vehicles != n) rc = AFE_ERR_INVALID_ARG;
   if (rc != AFE_OK) { delete m; return rc; }
+  m->device = acc.device;
+  const afe_device_view &view = acc.view;
+  const hipStream_t stream = acc.stream;
   // one arena: [3][n] reference, six latch arrays, chunk table, edges, group_chunk0, partials
   const size_t N = (size_t)n, NC = (size_t)std::max<int64_t>(L.n_chunks, 1), NG = (size_t)n_groups + 1;
   size_t off = 0;

@@ -21,7 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "afe_render.h"   // engine_stream_device
+#include "afe_consumer.h"   // engine_stream_device
 #include "afe_world.h"
 
 namespace afe {

@@ -84,6 +84,26 @@ def test_no_device_means_loud_failure_not_fallback(afa):
     assert ei.value.status == 2  # AFE_ERR_NO_DEVICE
 
 
+def test_no_device_refuses_the_planner_and_the_device_buffer(afa):
+    """the two other callers of the shared device picker (afe_consumer.h pick_gfx950): afe_rappids_plan, afe_device_alloc"""
+    import torch
+    cfg = afa.planner_default_config(64, 48, 10.0 / 256.0, 32.0, 0.116, 0.174, 0.5)
+    imgs = np.full((1, 48, 64), 255, np.uint16)
+    vel0, zeros, grav = np.array([[0.0], [0.0], [1.0]]), np.zeros((3, 1)), np.array([[0.0], [9.81], [0.0]])
+    samples = afa.planner_samples(0, 64, 48, 8)
+    if torch.cuda.is_available():
+        afa.DeviceBuffer(64).close()
+        out, _, _ = afa.rappids_plan(cfg, imgs, vel0, zeros, grav, samples)
+        assert len(out) == 1
+        return
+    with pytest.raises(afa.AfeError) as ei:
+        afa.DeviceBuffer(64)
+    assert ei.value.status == 2  # AFE_ERR_NO_DEVICE
+    with pytest.raises(afa.AfeError) as ei:
+        afa.rappids_plan(cfg, imgs, vel0, zeros, grav, samples)
+    assert ei.value.status == 2  # AFE_ERR_NO_DEVICE
+
+
 def test_product_never_imports_the_oracle():
     """only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may import,
     link or call anything under oracle/"""

@@ -402,3 +402,71 @@ def test_map_and_engine_on_different_devices_are_refused(small):
     assert ei.value.status == 1
     e.close()
     other.close()
+
+
+# ---- 8. one pose function --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("precision", [AFE_F32, AFE_F64])
+def test_camera_and_audit_place_a_vehicle_with_the_same_pose(small, ora, precision):
+    """afe_render_depth_engine and afe_clearance_plans_engine form origin and matrix with one function (afe_pose.h), and it is
+    the one both judges state: large turns, the camera's mount, fp32 slabs with anchors.  Neither entry hands its pose out, so
+    each is taken through what it does with it.  The audit: plans whose polynomial is constant -- zero and the three unit
+    vectors -- are sampled at o and at o + column j of R, and the records of those points must be the checker's at its pose.
+    The camera: 64 views of one triangle must be the camera checker's images, which it renders at its pose.  The two
+    judges' poses are compared directly, bit for bit."""
+    tris, cmap = small
+    n = 64
+    rng = np.random.default_rng(41)
+    pos = np.stack([rng.uniform(-60, 60, n), rng.uniform(-60, 60, n), rng.uniform(0.5, 3.0, n)])
+    att = scen.random_attitudes(rng, n, max_tilt_deg=180.0)
+    assert (np.abs(att[0]) < 0.5).sum() >= n // 4           # turns by more than 120 degrees are there
+    params = afa.params_from_type(5)
+    e = afa.Ensemble(n, precision=precision)
+    e.set_type_table([params])
+    e.set_state(pos, rng.normal(0, 2.0, (3, n)), att, np.zeros((3, n)), np.full((4, n), scen.hover_speed(params)))
+    e.set_motor_cmds(np.full((4, n), scen.hover_speed(params), np.float32))
+    e.step(1000, 5)                                          # fp32: x and y are now anchor + a non-zero offset
+    mount = afa.camera_default_mount()
+    assert np.abs(mount - [1.0, 0.0, 0.0, 0.0]).max() > 0.4
+    st = e.get_state()
+    assert (st["pos"][:2] != pos[:2]).any()
+    # the judges' poses
+    L = ora.render_lib()
+    origin, rot = np.empty((3, n)), np.empty((9, n))
+    for i in range(n):
+        origin[:, i], rot[:, i] = pc.camera_pose(st["pos"][:, i], st["att"][:, i], mount)
+        q, R = np.empty(4), np.empty(9)
+        L.ora_quat_mul(ora._dp(np.ascontiguousarray(st["att"][:, i], dtype=float)), ora._dp(np.ascontiguousarray(mount, dtype=float)), ora._dp(q))
+        L.ora_quat_to_matrix(ora._dp(q), ora._dp(R))
+        assert_array_equal(R.view(np.uint64), rot[:, i].view(np.uint64))
+    assert_array_equal(origin.view(np.uint64), np.ascontiguousarray(st["pos"], dtype=np.float64).view(np.uint64))
+    # the camera
+    one = np.array([[40.0, -90.0, -20.0, 40.0, 90.0, -20.0, 40.0, 0.0, 60.0]], np.float32)
+    scene = afa.Scene(one)
+    cam = afa.camera_default(16, 12)
+    cam.depth_scale, cam.max_count = 0.01, 65535
+    imgs, _ = scene.render_engine(e, cam, mount)
+    oc = ora.render_camera(cam.width, cam.height, cam.focal_length, cam.depth_scale, cam.max_count)
+    seen = 0
+    for i in range(n):
+        want = ora.render_depth(oc, one, st["pos"][:, i], st["att"][:, i], mount)
+        assert_array_equal(imgs[i], want, err_msg="view %d" % i)
+        seen += int((want < cam.max_count).any())
+    assert seen >= 8                                         # the triangle is in sight of some views, out of sight of others
+    assert seen <= n - 8
+    scene.close()
+    # the audit
+    K = 2
+    tr = np.stack([np.zeros(n), np.ones(n)])
+    for axis in (None, 0, 1, 2):
+        plans = np.zeros(n, afa.PLAN_DTYPE)
+        plans["found"] = 1
+        plans["tf"] = 1.0
+        if axis is not None:
+            plans["coeffs"][:, 5, axis] = 1.0
+        want, want_col = pc.audit(tris, plans["coeffs"], tr, origin, rot, K, RADIUS)
+        assert np.isfinite(want["min_dist2"]).all()
+        got, n_col, _ = cmap.plans_engine(e, plans, mount, n_samples=K, radius=RADIUS)
+        pc.assert_records_equal(got, want)
+        assert n_col == want_col
+    e.close()

@@ -84,3 +84,18 @@ int main() {
                            os.path.join(csrc, "afe_params.cpp"), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
+
+
+def test_consumer_helpers_release_everything_on_their_failure_paths(tmp_path):
+    """afe_consumer.h's StreamTimer and DevBuf (tests/cpp/test_consumer_raii.cpp) under ASan + UBSan on the host, every
+    device hidden from the program: each HIP call fails, and whatever was made before the failure must go with the scope"""
+    exe = tmp_path / "consumer_raii"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "-std=c++17", "-O1", "-g", "-x", "hip", "--offload-arch=gfx950",
+                           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "agri-fly_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "test_consumer_raii.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True,
+                         env=dict(os.environ, ROCR_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, (out.stdout + out.stderr)[-2000:]
+    assert out.stdout.strip() == "ok" and not out.stderr.strip(), out.stderr[-2000:]
