@@ -23,10 +23,12 @@ from .engine import (  # noqa: F401
     AFE_STEP_RESIDENT,
     AfeError,
     Camera,
+    CONSERVATIVENESS_DTYPE,
     ClearanceMap,
     ContactMonitor,
     GROUP_STATS_DTYPE,
     GroupStats,
+    IMAGE_TRUTH_DTYPE,
     PATH_CLEARANCE_DTYPE,
     PLAN_DTYPE,
     PathClearance,
@@ -50,6 +52,10 @@ from .engine import (  # noqa: F401
     camera_default,
     clearance_check_hierarchy,
     gather_exchange,
+    image_truth_candidates,
+    image_truth_paths,
+    image_truth_plans,
+    image_truth_sample_times,
     camera_default_mount,
     library,
     library_path,

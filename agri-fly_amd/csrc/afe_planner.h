@@ -1,5 +1,8 @@
 // afe_planner.h -- structures shared by the planner kernel and its host entry point.
 #pragma once
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include "../../include/agrifly_engine.h"
@@ -72,5 +75,91 @@ struct PlannerBatch {
 };
 
 int launch_rappids(const PlannerConfig &cfg, const PlannerBatch &b, void *stream);
+
+#if defined(__HIPCC__) && !defined(AFE_PLANNER_NO_DEVICE_MATH)
+// The candidate's arithmetic, shared by the planner (afe_planner.hip) and the image ground truth (afe_truth.hip): both
+// must form a candidate's coefficients with the same operations in the same order, so there is one copy.  Internal
+// linkage, as when they lived in afe_planner.hip; a host-only includer defines AFE_PLANNER_NO_DEVICE_MATH.
+namespace {
+
+// ---- one candidate motion primitive (RTG + 3 x SAT) ------------------------
+struct Cand {
+  double v0[3], a0[3], grav[3];     // initial state (p0 = 0: camera-fixed frame) and gravity
+  double al[3], be[3], ga[3];       // SAT _a, _b, _g per axis
+  double peak[3][2];                // SAT _accPeakTimes
+  double tf;
+};
+
+__device__ double c_acc(const Cand &k, int i, double t) {  // SAT.hpp GetAcceleration
+#pragma clang fp contract(off)
+  return k.a0[i] + k.ga[i] * t + (1 / 2.0) * k.be[i] * t * t + (1 / 6.0) * k.al[i] * t * t * t;
+}
+__device__ double c_vel(const Cand &k, int i, double t) {
+#pragma clang fp contract(off)
+  return k.v0[i] + k.a0[i] * t + (1 / 2.0) * k.ga[i] * t * t + (1 / 6.0) * k.be[i] * t * t * t +
+         (1 / 24.0) * k.al[i] * t * t * t * t;
+}
+__device__ double c_pos(const Cand &k, int i, double t) {
+#pragma clang fp contract(off)
+  return 0.0 + k.v0[i] * t + (1 / 2.0) * k.a0[i] * t * t + (1 / 6.0) * k.ga[i] * t * t * t +
+         (1 / 24.0) * k.be[i] * t * t * t * t + (1 / 120.0) * k.al[i] * t * t * t * t * t;
+}
+
+// SAT.cpp:59-107 (goal position, velocity and acceleration all defined; goal velocity
+// and acceleration are zero for every RAPPIDS candidate, DIP.hpp:398-401) and the
+// acceleration peak times of SAT.cpp:119-140
+__device__ void c_generate(Cand &k, const double pf[3], double Tf) {
+#pragma clang fp contract(off)
+  const double T2 = Tf * Tf, T3 = T2 * Tf, T4 = T3 * Tf, T5 = T4 * Tf;
+  for (int i = 0; i < 3; i++) {
+    const double da = 0.0 - k.a0[i];
+    const double dv = 0.0 - k.v0[i] - k.a0[i] * Tf;
+    const double dp = pf[i] - 0.0 - k.v0[i] * Tf - 0.5 * k.a0[i] * Tf * Tf;
+    k.al[i] = (60 * T2 * da - 360 * Tf * dv + 720 * 1 * dp) / T5;
+    k.be[i] = (-24 * T3 * da + 168 * T2 * dv - 360 * Tf * dp) / T5;
+    k.ga[i] = (3 * T4 * da - 24 * T3 * dv + 60 * T2 * dp) / T5;
+    if (k.al[i]) {
+      const double det = k.be[i] * k.be[i] - 2 * k.ga[i] * k.al[i];
+      if (det < 0) {
+        k.peak[i][0] = 0;
+        k.peak[i][1] = 0;
+      } else {
+        k.peak[i][0] = (-k.be[i] + sqrt(det)) / k.al[i];
+        k.peak[i][1] = (-k.be[i] - sqrt(det)) / k.al[i];
+      }
+    } else {
+      k.peak[i][0] = k.be[i] ? -k.ga[i] / k.be[i] : 0;
+      k.peak[i][1] = 0;
+    }
+  }
+  k.tf = Tf;
+}
+
+// ---- CommonMath::Trajectory: c[0] t^5 + ... + c[5] --------------------------
+struct Poly {
+  double c[6][3];
+};
+
+__device__ void deproject(const PlannerConfig &c, double x, double y, double depth, double o[3]) {
+#pragma clang fp contract(off)
+  o[0] = depth * ((x - c.cx) / c.focal_length);   // DIP.hpp:274-279
+  o[1] = depth * ((y - c.cy) / c.focal_length);
+  o[2] = depth * 1;
+}
+
+__device__ __forceinline__ void candidate_poly(const Cand &k, Poly &p) {   // RTG.hpp GetTrajectory
+#pragma clang fp contract(off)
+  for (int a = 0; a < 3; a++) {
+    p.c[0][a] = k.al[a] / 120;
+    p.c[1][a] = k.be[a] / 24;
+    p.c[2][a] = k.ga[a] / 6;
+    p.c[3][a] = c_acc(k, a, 0) / 2;
+    p.c[4][a] = c_vel(k, a, 0);
+    p.c[5][a] = c_pos(k, a, 0);
+  }
+}
+
+}  // namespace
+#endif  // __HIPCC__ && !AFE_PLANNER_NO_DEVICE_MATH
 
 }  // namespace afe

@@ -150,61 +150,10 @@ __device__ void sort_small(double *a, int n) {
   }
 }
 
-// ---- one candidate motion primitive (RTG + 3 x SAT) ------------------------
-struct Cand {
-  double v0[3], a0[3], grav[3];     // initial state (p0 = 0: camera-fixed frame) and gravity
-  double al[3], be[3], ga[3];       // SAT _a, _b, _g per axis
-  double peak[3][2];                // SAT _accPeakTimes
-  double tf;
-};
-
-__device__ double c_acc(const Cand &k, int i, double t) {  // SAT.hpp GetAcceleration
-#pragma clang fp contract(off)
-  return k.a0[i] + k.ga[i] * t + (1 / 2.0) * k.be[i] * t * t + (1 / 6.0) * k.al[i] * t * t * t;
-}
-__device__ double c_vel(const Cand &k, int i, double t) {
-#pragma clang fp contract(off)
-  return k.v0[i] + k.a0[i] * t + (1 / 2.0) * k.ga[i] * t * t + (1 / 6.0) * k.be[i] * t * t * t +
-         (1 / 24.0) * k.al[i] * t * t * t * t;
-}
-__device__ double c_pos(const Cand &k, int i, double t) {
-#pragma clang fp contract(off)
-  return 0.0 + k.v0[i] * t + (1 / 2.0) * k.a0[i] * t * t + (1 / 6.0) * k.ga[i] * t * t * t +
-         (1 / 24.0) * k.be[i] * t * t * t * t + (1 / 120.0) * k.al[i] * t * t * t * t * t;
-}
+// ---- one candidate motion primitive (RTG + 3 x SAT): Cand, c_acc, c_vel, c_pos, c_generate are in afe_planner.h ----
 __device__ double c_jerk(const Cand &k, int i, double t) {
 #pragma clang fp contract(off)
   return k.ga[i] + k.be[i] * t + (1 / 2.0) * k.al[i] * t * t;
-}
-
-// SAT.cpp:59-107 (goal position, velocity and acceleration all defined; goal velocity
-// and acceleration are zero for every RAPPIDS candidate, DIP.hpp:398-401) and the
-// acceleration peak times of SAT.cpp:119-140
-__device__ void c_generate(Cand &k, const double pf[3], double Tf) {
-#pragma clang fp contract(off)
-  const double T2 = Tf * Tf, T3 = T2 * Tf, T4 = T3 * Tf, T5 = T4 * Tf;
-  for (int i = 0; i < 3; i++) {
-    const double da = 0.0 - k.a0[i];
-    const double dv = 0.0 - k.v0[i] - k.a0[i] * Tf;
-    const double dp = pf[i] - 0.0 - k.v0[i] * Tf - 0.5 * k.a0[i] * Tf * Tf;
-    k.al[i] = (60 * T2 * da - 360 * Tf * dv + 720 * 1 * dp) / T5;
-    k.be[i] = (-24 * T3 * da + 168 * T2 * dv - 360 * Tf * dp) / T5;
-    k.ga[i] = (3 * T4 * da - 24 * T3 * dv + 60 * T2 * dp) / T5;
-    if (k.al[i]) {
-      const double det = k.be[i] * k.be[i] - 2 * k.ga[i] * k.al[i];
-      if (det < 0) {
-        k.peak[i][0] = 0;
-        k.peak[i][1] = 0;
-      } else {
-        k.peak[i][0] = (-k.be[i] + sqrt(det)) / k.al[i];
-        k.peak[i][1] = (-k.be[i] - sqrt(det)) / k.al[i];
-      }
-    } else {
-      k.peak[i][0] = k.be[i] ? -k.ga[i] / k.be[i] : 0;
-      k.peak[i][1] = 0;
-    }
-  }
-  k.tf = Tf;
 }
 
 __device__ double c_thrust(const Cand &k, double t) {  // RTG.hpp GetThrust
@@ -308,9 +257,7 @@ __device__ bool velocity_feasible(const Cand &k, double vmax) {
 }
 
 // ---- CommonMath::Trajectory: c[0] t^5 + ... + c[5] --------------------------
-struct Poly {
-  double c[6][3];
-};
+// (struct Poly: afe_planner.h)
 __device__ double p_axis(const Poly &p, int i, double t) {  // Trajectory.hpp:90-96
 #pragma clang fp contract(off)
   return p.c[0][i] * t * t * t * t * t + p.c[1][i] * t * t * t * t + p.c[2][i] * t * t * t + p.c[3][i] * t * t +
@@ -335,12 +282,7 @@ __device__ void unit_normal(const double a[3], const double b[3], double o[3]) {
   const float n = (float)sqrt(x * x + y * y + z * z);
   o[0] = x / n; o[1] = y / n; o[2] = z / n;
 }
-__device__ void deproject(const PlannerConfig &c, double x, double y, double depth, double o[3]) {
-#pragma clang fp contract(off)
-  o[0] = depth * ((x - c.cx) / c.focal_length);   // DIP.hpp:274-279
-  o[1] = depth * ((y - c.cy) / c.focal_length);
-  o[2] = depth * 1;
-}
+// (deproject: afe_planner.h)
 
 // shrink bookkeeping shared by the eight scans of DIP.cpp:617-940
 #ifndef AFE_SHRINK_QUAL
@@ -1337,17 +1279,7 @@ __device__ __forceinline__ double candidate_cost(const PlannerConfig &cfg, const
 
 enum { CAND_INPUT_FEASIBLE = 1, CAND_VELOCITY_OK = 2 };
 
-__device__ __forceinline__ void candidate_poly(const Cand &k, Poly &p) {   // RTG.hpp GetTrajectory
-#pragma clang fp contract(off)
-  for (int a = 0; a < 3; a++) {
-    p.c[0][a] = k.al[a] / 120;
-    p.c[1][a] = k.be[a] / 24;
-    p.c[2][a] = k.ga[a] / 6;
-    p.c[3][a] = c_acc(k, a, 0) / 2;
-    p.c[4][a] = c_vel(k, a, 0);
-    p.c[5][a] = c_pos(k, a, 0);
-  }
-}
+// (candidate_poly, the winner's conversion: afe_planner.h)
 
 __global__ void __launch_bounds__(256) afe_rappids_candidates_kernel(const PlannerConfig cfg, const PlannerBatch b) {
 #pragma clang fp contract(off)

@@ -9,6 +9,7 @@
 
 #include "afe_consumer.h"
 #include "afe_host.h"   // afe_dev_env
+#define AFE_PLANNER_NO_DEVICE_MATH      // the structures alone
 #include "afe_planner.h"
 
 using namespace afe;

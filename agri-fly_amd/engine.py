@@ -56,6 +56,8 @@ ABI_FUNCTIONS = [
     "afe_contact_monitor_destroy",
     "afe_stats_check_layout", "afe_stats_create", "afe_stats_destroy", "afe_stats_info", "afe_stats_set_reference",
     "afe_stats_set_histogram", "afe_stats_update", "afe_stats_get", "afe_stats_reset",
+    "afe_image_truth_sample_times", "afe_image_truth_paths", "afe_image_truth_paths_stats", "afe_image_truth_plans",
+    "afe_image_truth_candidates", "afe_device_upload",
 ]
 
 
@@ -337,6 +339,7 @@ def library():
         "afe_device_alloc": [ci, u64, C.POINTER(vp)],
         "afe_device_free": [vp],
         "afe_device_download": [vp, vp, u64],
+        "afe_device_upload": [vp, vp, u64],
         "afe_checkpoint_size": [eng, C.POINTER(u64)],
         "afe_save_checkpoint": [eng, vp, u64],
         "afe_load_checkpoint": [eng, vp, u64],
@@ -394,6 +397,12 @@ def library():
         "afe_stats_update": [vp, vp, vp],
         "afe_stats_get": [vp, i64, i64, vp, vp, vp, vp, vp, vp],
         "afe_stats_reset": [vp, i64, i64],
+        "afe_image_truth_sample_times": [C.c_double, C.c_double, C.c_double, C.POINTER(ci), vp],
+        "afe_image_truth_paths": [ci, C.POINTER(PlannerConfig), i64, vp, i64, ci, vp, vp, vp, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "afe_image_truth_paths_stats": [ci, C.POINTER(PlannerConfig), i64, vp, i64, ci, vp, vp, vp, C.c_double, vp, C.POINTER(C.c_float)],
+        "afe_image_truth_plans": [ci, C.POINTER(PlannerConfig), i64, vp, i64, ci, vp, vp, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "afe_image_truth_candidates": [ci, C.POINTER(PlannerConfig), i64, vp, i64, ci, vp, vp, vp, vp, ci, vp, ci, vp, C.c_double, vp, vp, vp, vp,
+                                       C.POINTER(C.c_float)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -545,6 +554,13 @@ class DeviceBuffer:
         if rc:
             raise AfeError(rc, library().afe_status_string(rc).decode())
         return out
+
+    def upload(self, array, offset_bytes=0):
+        a = np.ascontiguousarray(array)
+        assert offset_bytes >= 0 and offset_bytes + a.nbytes <= self.nbytes
+        rc = library().afe_device_upload(C.c_void_p(self.ptr.value + int(offset_bytes)), a.ctypes.data, a.nbytes)
+        if rc:
+            raise AfeError(rc, library().afe_status_string(rc).decode())
 
     def close(self):
         if self.ptr:
@@ -813,6 +829,108 @@ class ClearanceMap:
                                                      p_ptr, int(n_samples), float(radius), float(max_dist), out.ctypes.data,
                                                      C.byref(nc), C.byref(ms)))
         return out, nc.value, ms.value
+
+
+# afe_image_truth: what one sampled path did against the depth image (8-byte members only, 64 bytes)
+IMAGE_TRUTH_DTYPE = np.dtype([("verdict", np.int64), ("k_fov", np.int64), ("t_fov", np.float64), ("k_hit", np.int64),
+                              ("t_hit", np.float64), ("pixel_hit", np.int64), ("n_samples", np.int64), ("n_checked", np.int64)])
+# afe_conservativeness: MeasureConservativeness' tally
+CONSERVATIVENESS_DTYPE = np.dtype([(k, np.int64) for k in ("n_checked", "n_planner_free", "n_correct_in_collision",
+                                                           "n_incorrect_in_collision", "n_free_but_out_of_view", "n_free_but_occluded")])
+
+
+def image_truth_sample_times(t_begin, t_end, timestep=0.1):
+    """Host-only: the ground truth's sample times over [t_begin, t_end), the running sum t_{k+1} = t_k + timestep."""
+    k = C.c_int(0)
+    _status(library().afe_image_truth_sample_times(float(t_begin), float(t_end), float(timestep), C.byref(k), None))
+    t = np.empty(k.value)
+    _status(library().afe_image_truth_sample_times(float(t_begin), float(t_end), float(timestep), C.byref(k), t.ctypes.data))
+    return t
+
+
+def _truth_images(cfg, depth_images, image_index, n_owners):
+    """(keep-alive, pointer, n_images, on_device, index keep-alive, index pointer) of the image arguments"""
+    if isinstance(depth_images, DeviceBuffer):
+        img, ptr, n_images, on_device = depth_images, depth_images.ptr, depth_images.nbytes // (2 * cfg.height * cfg.width), 1
+    else:
+        img = np.ascontiguousarray(depth_images, dtype=np.uint16)
+        if img.ndim == 2:
+            img = img[None]
+        assert img.shape[1:] == (cfg.height, cfg.width), (img.shape, cfg.height, cfg.width)
+        ptr, n_images, on_device = img.ctypes.data, img.shape[0], 0
+    idx = None if image_index is None else np.ascontiguousarray(image_index, dtype=np.int32)
+    assert idx is None or idx.shape == (n_owners,)
+    return img, ptr, n_images, on_device, idx, None if idx is None else idx.ctypes.data
+
+
+def image_truth_paths(cfg, depth_images, coeffs, t_range, image_index=None, timestep=0.1, device=-1, want_stats=False):
+    """The reference's IsCollisionFreeGroundTruth for n explicit camera-frame paths: depth_images uint16 [n_images, H, W] or a
+    DeviceBuffer holding them, coeffs [n, 6, 3] (t^5 .. t^0 per axis), t_range [2, n] = [t_begin, t_end) ->
+    (records: IMAGE_TRUTH_DTYPE [n], n_free, kernel_ms); verdict 0 free, 1 out of view, 2 occluded.
+    want_stats: the scan's counters instead (counting build): (dict, kernel_ms)."""
+    c = np.ascontiguousarray(coeffs, dtype=np.float64)
+    n = c.shape[0]
+    assert c.shape == (n, 6, 3)
+    tr = np.ascontiguousarray(t_range, dtype=np.float64)
+    assert tr.shape == (2, n)
+    _img, ptr, n_images, on_device, _idx, idx_ptr = _truth_images(cfg, depth_images, image_index, n)
+    ms = C.c_float(0)
+    if want_stats:
+        st = np.zeros(4, np.uint64)
+        _status(library().afe_image_truth_paths_stats(int(device), C.byref(cfg), n, ptr, n_images, on_device, idx_ptr, c.ctypes.data,
+                                                      tr.ctypes.data, float(timestep), st.ctypes.data, C.byref(ms)))
+        return dict(zip(("samples", "pixels_tested", "pixels_meeting_sphere", "pixels_brute_force"), (int(x) for x in st))), ms.value
+    out = np.empty(n, IMAGE_TRUTH_DTYPE)
+    nf = C.c_int64(0)
+    _status(library().afe_image_truth_paths(int(device), C.byref(cfg), n, ptr, n_images, on_device, idx_ptr, c.ctypes.data, tr.ctypes.data,
+                                            float(timestep), out.ctypes.data, C.byref(nf), C.byref(ms)))
+    return out, nf.value, ms.value
+
+
+def image_truth_plans(cfg, depth_images, plans, image_index=None, timestep=0.1, device=-1):
+    """The same for the plans rappids_plan returned (a PlanOutput array or a PLAN_DTYPE array), each over [0, tf); a plan with
+    found == 0 gets the empty record (verdict -1) -> (records: IMAGE_TRUTH_DTYPE [n], n_free, kernel_ms)."""
+    if isinstance(plans, np.ndarray):
+        assert plans.dtype == PLAN_DTYPE
+        p = np.ascontiguousarray(plans)
+        n, p_ptr = p.size, p.ctypes.data
+    else:
+        p, n, p_ptr = plans, len(plans), C.cast(plans, C.c_void_p)
+    _img, ptr, n_images, on_device, _idx, idx_ptr = _truth_images(cfg, depth_images, image_index, n)
+    out = np.empty(n, IMAGE_TRUTH_DTYPE)
+    nf, ms = C.c_int64(0), C.c_float(0)
+    _status(library().afe_image_truth_plans(int(device), C.byref(cfg), n, ptr, n_images, on_device, idx_ptr, p_ptr, float(timestep),
+                                            out.ctypes.data, C.byref(nf), C.byref(ms)))
+    return out, nf.value, ms.value
+
+
+def image_truth_candidates(cfg, depth_images, vel0, acc0, samples, flags, image_index=None, sample_table=None, timestep=0.1,
+                           want_coeffs=False, want_per_planner=False, device=-1):
+    """The reference's MeasureConservativeness for n planners x M candidates: the arguments of rappids_plan and the flags [n, M]
+    it returned -> (verdicts uint8 [n, M], coeffs [n, M, 6, 3] or None, tally: CONSERVATIVENESS_DTYPE scalar,
+    per_planner: CONSERVATIVENESS_DTYPE [n] or None, kernel_ms).  Every candidate gets a verdict; only those the planner
+    collision-checked (flag bit 4) are tallied."""
+    v = np.ascontiguousarray(vel0, dtype=np.float64)
+    n = v.shape[1]
+    a = np.ascontiguousarray(acc0, dtype=np.float64)
+    s = np.ascontiguousarray(samples, dtype=np.float64)
+    if s.ndim == 2:
+        s = s[None]
+    m = s.shape[1]
+    fl = np.ascontiguousarray(flags, dtype=np.uint8)
+    assert v.shape == a.shape == (3, n) and s.shape[2] == 4 and fl.shape == (n, m)
+    _img, ptr, n_images, on_device, _idx, idx_ptr = _truth_images(cfg, depth_images, image_index, n)
+    st = None if sample_table is None else np.ascontiguousarray(sample_table, dtype=np.int32)
+    verdict = np.empty((n, m), np.uint8)
+    co = np.empty((n, m, 6, 3)) if want_coeffs else None
+    tally = np.zeros(1, CONSERVATIVENESS_DTYPE)
+    per = np.zeros(n, CONSERVATIVENESS_DTYPE) if want_per_planner else None
+    ms = C.c_float(0)
+    _status(library().afe_image_truth_candidates(int(device), C.byref(cfg), n, ptr, n_images, on_device, idx_ptr, v.ctypes.data, a.ctypes.data,
+                                                 s.ctypes.data, s.shape[0], None if st is None else st.ctypes.data, m, fl.ctypes.data,
+                                                 float(timestep), verdict.ctypes.data, None if co is None else co.ctypes.data,
+                                                 tally.ctypes.data, None if per is None else per.ctypes.data, C.byref(ms)))
+    return verdict, co, tally[0], per, ms.value
 
 
 def clearance_check_hierarchy(triangles):

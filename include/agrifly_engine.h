@@ -525,6 +525,76 @@ int afe_clearance_plans_engine(afe_engine *e, afe_clearance_map *m, int64_t firs
                                double radius, double max_dist, afe_path_clearance *out,
                                int64_t *n_colliding, float *kernel_ms);
 
+/* ---- image truth: the planner's own self-evaluation (DepthImagePlanner.cpp:1031-1098 IsCollisionFreeGroundTruth and
+ * :972-1002 MeasureConservativeness, Section IV.A of the RAPPIDS paper) --------------------------------------------
+ * Against the depth image the planner saw: a path (coeffs[6][3] = t^5 .. t^0, the layout of afe_plan_output::coeffs,
+ * camera frame, over [t_begin, t_end)) is sampled at t_0 = t_begin, t_{k+1} = t_k + timestep while t_k < t_end (the
+ * reference's running sum; it uses timestep = 0.1).  Samples nearer than cfg->min_checking_dist are skipped.  First
+ * every sample's projection must keep edge = int(f * true_vehicle_radius / min_checking_dist) pixels from the image
+ * border (else verdict 1: out of view, at the lowest such sample, and no pixel is looked at); then, sample by sample,
+ * every pixel deeper than ignore = uint16(true_vehicle_radius / depth_scale) whose ray meets the sphere of
+ * planning_vehicle_radius about the sample must lie behind it (else verdict 2: occluded, at the first such sample;
+ * pixel_hit = the lowest y*width + x among its occluding pixels).  Verdict 0: free.  csrc/afe_truth.hip states every
+ * operation, tests/truth_checker.py restates it; the two agree bit for bit.
+ *   n_samples   K (more than 4096: AFE_ERR_OUT_OF_RANGE)
+ *   n_checked   samples whose pixels were examined, up to and including k_hit (0 with verdict 1)
+ *   absent fields are -1 / NaN;  the empty record (a plan with found == 0): verdict -1, every index -1, NaNs, counts 0
+ * Refused before any launch, outputs untouched: NULLs, width or height <= 0, timestep not finite or <= 0, a device
+ * image pointer that is not 16-byte aligned, fewer images than paths without image_index (AFE_ERR_INVALID_ARG);
+ * width*height > 2^24, min_checking_dist <= 0, true_vehicle_radius / depth_scale not in (-1, 65536), an edge beyond
+ * 2^30, an image_index entry outside [0, n_images), K > 4096 (AFE_ERR_OUT_OF_RANGE).
+ * What sampling does NOT cover: between two samples a path can be occluded where it is free at both. */
+typedef struct afe_image_truth {         /* 8-byte members only, 64 bytes; the layout is ABI */
+  int64_t verdict, k_fov;
+  double  t_fov;
+  int64_t k_hit;
+  double  t_hit;
+  int64_t pixel_hit, n_samples, n_checked;
+} afe_image_truth;
+typedef struct afe_conservativeness {    /* MeasureConservativeness' tally; 8-byte members only, 48 bytes */
+  int64_t n_checked;                /* candidates the planner collision-checked (flag bit 4 set) */
+  int64_t n_planner_free;           /* of those: the planner calls them collision-free (flag bit 8 set) */
+  int64_t n_correct_in_collision;   /* the planner rejects, the ground truth too (verdict != 0) */
+  int64_t n_incorrect_in_collision; /* the planner rejects, the ground truth calls it free (verdict == 0) */
+  int64_t n_free_but_out_of_view;   /* the planner accepts, verdict 1 */
+  int64_t n_free_but_occluded;      /* the planner accepts, verdict 2 */
+} afe_conservativeness;
+
+/* Pure host (no GPU): the definition's sample count and, if t_out is not NULL, the times t_out[*n_samples] (room for
+ * 4096).  K > 4096: AFE_ERR_OUT_OF_RANGE, nothing written. */
+int afe_image_truth_sample_times(double t_begin, double t_end, double timestep, int *n_samples, double *t_out);
+
+/* n_paths explicit paths on GPU `device` (< 0: current): coeffs [n][6][3]; t_range planar [2][n].  images
+ * [n_images][height][width] uint16: a host array, or (images_on_device != 0) a 16-byte-aligned device pointer, e.g.
+ * what afe_render_depth_engine filled.  image_index [n_paths] (host) or NULL (image i for path i).  out: n_paths
+ * records.  n_free (optional): the number of records with verdict 0, summed on the device.  n_paths == 0 is AFE_OK. */
+int afe_image_truth_paths(int device, const afe_planner_config *cfg, int64_t n_paths, const void *images,
+                          int64_t n_images, int images_on_device, const int32_t *image_index, const double *coeffs,
+                          const double *t_range, double timestep, afe_image_truth *out, int64_t *n_free,
+                          float *kernel_ms);
+/* What the scan did for such a batch (a counting build of the same kernel; the records are discarded): stats[0]
+ * samples whose pixels were examined, [1] pixels tested for s, [2] pixels whose ray met the sphere (s >= 0),
+ * [3] width * height * stats[0], what visiting every pixel would have tested. */
+int afe_image_truth_paths_stats(int device, const afe_planner_config *cfg, int64_t n_paths, const void *images,
+                                int64_t n_images, int images_on_device, const int32_t *image_index,
+                                const double *coeffs, const double *t_range, double timestep, uint64_t stats[4],
+                                float *kernel_ms);
+/* The plans afe_rappids_plan* returned, each over [0, tf); found == 0 gives the empty record. */
+int afe_image_truth_plans(int device, const afe_planner_config *cfg, int64_t n, const void *images, int64_t n_images,
+                          int images_on_device, const int32_t *image_index, const afe_plan_output *plans,
+                          double timestep, afe_image_truth *out, int64_t *n_free, float *kernel_ms);
+/* MeasureConservativeness for n planners x n_candidates candidates: vel0, acc0, samples, sample_table as given to
+ * afe_rappids_plan*, flags [n][n_candidates] as it filled them.  EVERY candidate is formed (by the planner's own
+ * functions: coeffs_out [n][n_candidates][6][3], optional, holds what was judged) and judged over [0, duration):
+ * verdict_out [n][n_candidates] bytes.  Only candidates the planner collision-checked (flag bit 4) are tallied, on the
+ * device, in integers: tally = the sum over all planners, per_planner [n] (optional) each planner's own. */
+int afe_image_truth_candidates(int device, const afe_planner_config *cfg, int64_t n, const void *images,
+                               int64_t n_images, int images_on_device, const int32_t *image_index,
+                               const double *vel0, const double *acc0, const double *samples, int n_tables,
+                               const int32_t *sample_table, int n_candidates, const uint8_t *flags, double timestep,
+                               uint8_t *verdict_out, double *coeffs_out, afe_conservativeness *tally,
+                               afe_conservativeness *per_planner, float *kernel_ms);
+
 /* Per-vehicle latches, device resident, for a closed loop that wants to know about contact without downloading
  * the state: 0 < contact_radius <= search_radius, both finite.  The monitor BORROWS engine and map: destroy it
  * before either of them (not tracked). */
@@ -608,6 +678,7 @@ int afe_stats_reset(afe_stats_monitor *m, int64_t first, int64_t count);
 int afe_device_alloc(int device, uint64_t bytes, void **out);
 int afe_device_free(void *p);
 int afe_device_download(void *host_dst, const void *dev_src, uint64_t bytes);
+int afe_device_upload(void *dev_dst, const void *host_src, uint64_t bytes);   /* e.g. depth images for afe_image_truth_* */
 
 /* The planner keeps its device scratch between calls (grown on demand, one set per process; plan calls take
  * turns on it).  This gives the memory back; the next call allocates again. */
