@@ -30,6 +30,7 @@ from .engine import (  # noqa: F401
     GroupStats,
     IMAGE_TRUTH_DTYPE,
     PATH_CLEARANCE_DTYPE,
+    PATH_SWEEP_DTYPE,
     PLAN_DTYPE,
     PathClearance,
     StatsMonitor,
@@ -43,6 +44,7 @@ from .engine import (  # noqa: F401
     RADIO_PACKET_SIZE,
     RadioMessage,
     RatesLogicParams,
+    SEGMENT_CLEARANCE_DTYPE,
     Scene,
     TELEMETRY_PACKET_SIZE,
     TelemetryPacket,
@@ -60,6 +62,7 @@ from .engine import (  # noqa: F401
     library,
     library_path,
     params_from_type,
+    path_chord_deviation,
     path_sample_points,
     plan_ticks,
     planner_default_config,

@@ -54,6 +54,8 @@ ABI_FUNCTIONS = [
     "afe_path_sample_points", "afe_clearance_paths", "afe_clearance_paths_stats", "afe_clearance_plans_engine",
     "afe_contact_monitor_create", "afe_contact_monitor_update", "afe_contact_monitor_get", "afe_contact_monitor_reset",
     "afe_contact_monitor_destroy",
+    "afe_clearance_segments", "afe_clearance_segments_stats", "afe_clearance_paths_swept", "afe_clearance_paths_swept_stats",
+    "afe_clearance_plans_engine_swept", "afe_path_chord_deviation", "afe_contact_monitor_create_swept",
     "afe_stats_check_layout", "afe_stats_create", "afe_stats_destroy", "afe_stats_info", "afe_stats_set_reference",
     "afe_stats_set_histogram", "afe_stats_update", "afe_stats_get", "afe_stats_reset",
     "afe_image_truth_sample_times", "afe_image_truth_paths", "afe_image_truth_paths_stats", "afe_image_truth_plans",
@@ -388,6 +390,13 @@ def library():
         "afe_contact_monitor_get": [vp, i64, i64, vp, vp, vp],
         "afe_contact_monitor_reset": [vp, i64, i64],
         "afe_contact_monitor_destroy": [vp],
+        "afe_clearance_segments": [vp, i64, vp, vp, C.c_double, vp, C.POINTER(C.c_float)],
+        "afe_clearance_segments_stats": [vp, i64, vp, vp, C.c_double, vp, C.POINTER(C.c_float)],
+        "afe_clearance_paths_swept": [vp, i64, vp, vp, vp, vp, ci, C.c_double, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "afe_clearance_paths_swept_stats": [vp, i64, vp, vp, vp, vp, ci, C.c_double, C.c_double, vp, C.POINTER(C.c_float)],
+        "afe_clearance_plans_engine_swept": [eng, vp, i64, i64, vp, vp, ci, C.c_double, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "afe_path_chord_deviation": [vp, C.c_double, C.c_double, vp, ci, C.POINTER(C.c_double)],
+        "afe_contact_monitor_create_swept": [eng, vp, C.c_double, C.c_double, C.POINTER(vp)],
         "afe_stats_check_layout": [vp, ci, i64, C.POINTER(i64), C.POINTER(ci)],
         "afe_stats_create": [eng, vp, ci, C.POINTER(vp)],
         "afe_stats_destroy": [vp],
@@ -689,6 +698,24 @@ PATH_CLEARANCE_DTYPE = np.dtype([("min_dist2", np.float64), ("closest", np.float
                                  ("n_nonfinite", np.int64)])
 
 
+# afe_segment_clearance: one segment against the mesh (48 bytes); afe_path_sweep: afe_path_clearance over chords (112 bytes)
+SEGMENT_CLEARANCE_DTYPE = np.dtype([("dist2", np.float64), ("s", np.float64), ("closest", np.float64, (3,)), ("tri", np.int32), ("kind", np.int32)])
+PATH_SWEEP_DTYPE = np.dtype(PATH_CLEARANCE_DTYPE.descr + [("s_min", np.float64), ("s_first_hit", np.float64)])
+
+
+def path_chord_deviation(coeffs, t_begin, t_end, rot=None, n_samples=64):
+    """Host-only: an upper bound [m] on how far the quintic (coeffs [6, 3]) leaves the polyline of its n_samples sample points
+    (crude: h^2/8 max|p''| by triangle inequalities; see the header)."""
+    c = np.ascontiguousarray(coeffs, dtype=np.float64)
+    assert c.shape == (6, 3)
+    r = None if rot is None else np.ascontiguousarray(np.asarray(rot, np.float64).reshape(-1))
+    assert r is None or r.shape == (9,)
+    out = C.c_double(0)
+    _status(library().afe_path_chord_deviation(c.ctypes.data, float(t_begin), float(t_end), None if r is None else r.ctypes.data,
+                                               int(n_samples), C.byref(out)))
+    return out.value
+
+
 def _opt_f64(a, shape):
     if a is None:
         return None, None
@@ -761,6 +788,29 @@ class ClearanceMap:
         _status(library().afe_clearance_query_stats(self._h, p.shape[1], p.ctypes.data, float(max_dist), st.ctypes.data, C.byref(ms)))
         return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "points"), (int(x) for x in st))), ms.value
 
+    def _segment_arrays(self, p0, p1):
+        a, b = np.ascontiguousarray(p0, dtype=np.float64), np.ascontiguousarray(p1, dtype=np.float64)
+        n = a.shape[1]
+        assert a.shape == b.shape == (3, n)
+        return n, a, b
+
+    def segments(self, p0, p1, max_dist=np.inf):
+        """n segments p0 -> p1 ([3, n] each) -> (records: SEGMENT_CLEARANCE_DTYPE [n], kernel_ms): the exact squared distance
+        between each segment and the mesh (see the header, swept clearance)."""
+        n, a, b = self._segment_arrays(p0, p1)
+        out = np.empty(n, SEGMENT_CLEARANCE_DTYPE)
+        ms = C.c_float(0)
+        _status(library().afe_clearance_segments(self._h, n, a.ctypes.data, b.ctypes.data, float(max_dist), out.ctypes.data, C.byref(ms)))
+        return out, ms.value
+
+    def segments_stats(self, p0, p1, max_dist=np.inf):
+        """traversal counters of such a batch (counting build), summed over the segments: dict + kernel_ms"""
+        n, a, b = self._segment_arrays(p0, p1)
+        st = np.zeros(4, np.uint64)
+        ms = C.c_float(0)
+        _status(library().afe_clearance_segments_stats(self._h, n, a.ctypes.data, b.ctypes.data, float(max_dist), st.ctypes.data, C.byref(ms)))
+        return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "segments"), (int(x) for x in st))), ms.value
+
     def query_engine(self, ensemble, max_dist, first=0, count=None, out=None):
         """The same for vehicles [first, first+count) from the engine's device state.  out: None to get
         (dist2, tri, closest, kernel_ms) on the host, or a (dist2, tri, closest) tuple of DeviceBuffers (closest may
@@ -809,10 +859,38 @@ class ClearanceMap:
                                                     float(max_dist), st.ctypes.data, C.byref(ms)))
         return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "samples"), (int(x) for x in st))), ms.value
 
+    def paths_swept(self, coeffs, t_range, origin=None, rot=None, n_samples=64, radius=0.116, max_dist=np.inf):
+        """paths() over the n_samples - 1 chords between the sample points -> (records: PATH_SWEEP_DTYPE [n], n_colliding, kernel_ms)"""
+        n, _arrays, ptrs = self._path_arrays(coeffs, t_range, origin, rot)
+        out = np.empty(n, PATH_SWEEP_DTYPE)
+        nc, ms = C.c_int64(0), C.c_float(0)
+        _status(library().afe_clearance_paths_swept(self._h, n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(n_samples), float(radius),
+                                                    float(max_dist), out.ctypes.data, C.byref(nc), C.byref(ms)))
+        return out, nc.value, ms.value
+
+    def paths_swept_stats(self, coeffs, t_range, origin=None, rot=None, n_samples=64, radius=0.116, max_dist=np.inf):
+        """traversal counters of such a batch (counting build), summed over the chords: dict + kernel_ms"""
+        n, _arrays, ptrs = self._path_arrays(coeffs, t_range, origin, rot)
+        st = np.zeros(4, np.uint64)
+        ms = C.c_float(0)
+        _status(library().afe_clearance_paths_swept_stats(self._h, n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(n_samples), float(radius),
+                                                          float(max_dist), st.ctypes.data, C.byref(ms)))
+        return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "chords"), (int(x) for x in st))), ms.value
+
+    def plans_engine_swept(self, ensemble, plans, mount=None, first=0, count=None, n_samples=64, radius=0.116, max_dist=np.inf):
+        """plans_engine() over chords -> (records: PATH_SWEEP_DTYPE [count], n_colliding, kernel_ms)"""
+        return self._plans_engine(library().afe_clearance_plans_engine_swept, PATH_SWEEP_DTYPE, ensemble, plans, mount, first, count,
+                                  n_samples, radius, max_dist)
+
     def plans_engine(self, ensemble, plans, mount=None, first=0, count=None, n_samples=64, radius=0.116, max_dist=np.inf):
         """The plans of vehicles [first, first+count) as rappids_plan returned them (a PlanOutput array or a PLAN_DTYPE
         array, plans[i] for vehicle first + i), placed by each vehicle's pose on the device ->
         (records: PATH_CLEARANCE_DTYPE [count], n_colliding, kernel_ms)."""
+        return self._plans_engine(library().afe_clearance_plans_engine, PATH_CLEARANCE_DTYPE, ensemble, plans, mount, first, count,
+                                  n_samples, radius, max_dist)
+
+    def _plans_engine(self, entry, dtype, ensemble, plans, mount, first, count, n_samples, radius, max_dist):
+        """plans_engine and plans_engine_swept: the C entry and the dtype of its records"""
         count = ensemble.n - first if count is None else count
         if isinstance(plans, np.ndarray):
             assert plans.dtype == PLAN_DTYPE
@@ -823,11 +901,10 @@ class ClearanceMap:
             assert len(plans) >= count
             p, p_ptr = plans, C.cast(plans, C.c_void_p)
         m = None if mount is None else np.ascontiguousarray(mount, dtype=np.float64)
-        out = np.empty(max(count, 0), PATH_CLEARANCE_DTYPE)
+        out = np.empty(max(count, 0), dtype)
         nc, ms = C.c_int64(0), C.c_float(0)
-        _status(library().afe_clearance_plans_engine(ensemble.handle, self._h, int(first), int(count), None if m is None else m.ctypes.data,
-                                                     p_ptr, int(n_samples), float(radius), float(max_dist), out.ctypes.data,
-                                                     C.byref(nc), C.byref(ms)))
+        _status(entry(ensemble.handle, self._h, int(first), int(count), None if m is None else m.ctypes.data,
+                      p_ptr, int(n_samples), float(radius), float(max_dist), out.ctypes.data, C.byref(nc), C.byref(ms)))
         return out, nc.value, ms.value
 
 
@@ -943,16 +1020,19 @@ def clearance_check_hierarchy(triangles):
 
 class ContactMonitor:
     """afe_contact_monitor: per-vehicle closest approach and first contact, latched on the device.  Borrows the
-    ensemble and the map: close it before either of them."""
+    ensemble and the map: close it before either of them.  swept=True: every update measures the segment from the vehicle's
+    position at its last update to the current one (afe_contact_monitor_create_swept); reset() the vehicles you move with
+    set_state."""
 
     NEVER = np.uint64(0xffffffffffffffff)
 
-    def __init__(self, ensemble, cmap, contact_radius, search_radius):
+    def __init__(self, ensemble, cmap, contact_radius, search_radius, swept=False):
         self._h = C.c_void_p()
         self.n = ensemble.n
+        self.swept = bool(swept)
         self._keep = (ensemble, cmap)
-        _status(library().afe_contact_monitor_create(ensemble.handle, cmap.handle, float(contact_radius), float(search_radius),
-                                                     C.byref(self._h)))
+        create = library().afe_contact_monitor_create_swept if swept else library().afe_contact_monitor_create
+        _status(create(ensemble.handle, cmap.handle, float(contact_radius), float(search_radius), C.byref(self._h)))
 
     def update(self):
         """-> (vehicles in contact now, vehicles ever in contact)"""

@@ -440,9 +440,11 @@ int afe_render_depth_engine(afe_engine *e, afe_scene *s, const afe_camera *cam, 
  * that every bit of the answer is specified: csrc/afe_clearance.hip states the
  * expression tree).  The vehicle is a point: compare with the square of its
  * radius.  Contact is reported, the physics does not react to it.
- * Not covered: swept tests between two queries.  A monitor updated at 100 Hz
- * sees a vehicle at the planner's 5 m/s limit every 5 cm, against a vehicle
- * radius of 11.6 cm; thinner obstacles or faster vehicles need a higher rate. */
+ * A point query sees a vehicle only where it is asked: a monitor updated at
+ * 100 Hz sees a vehicle at the planner's 5 m/s limit every 5 cm, against a
+ * vehicle radius of 11.6 cm.  What lies between two queries is covered by the
+ * swept entries below (afe_clearance_segments,
+ * afe_contact_monitor_create_swept, afe_clearance_paths_swept). */
 typedef struct afe_clearance_map afe_clearance_map;
 /* triangles: n_tri x 9 floats (v0, v1, v2), finite.  device < 0: current device. */
 int afe_clearance_map_create(int device, const float *triangles, int64_t n_tri, afe_clearance_map **out);
@@ -489,8 +491,8 @@ int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, int64_t firs
  *                 bitwise-equal minima;  tri_min, closest[3], t_min from that sample.  None: +inf, -1, -1, NaN, NaN.
  * 0 < radius <= max_dist, radius finite, max_dist may be +inf (else AFE_ERR_INVALID_ARG).  max_dist only limits what is
  * reported as the closest approach (and lets the search prune); the hit fields do not depend on it.
- * What sampling does NOT cover: between two samples a path can come closer than at both.  The caller chooses K; for a
- * spacing no larger than the radius, K >= 1 + path length / radius.  A continuous swept test is not provided. */
+ * Between two samples a path can come closer than at both: afe_clearance_paths_swept below measures the chords between
+ * the samples instead, and afe_path_chord_deviation bounds how far the curve leaves them. */
 typedef struct afe_path_clearance {      /* 8-byte members only, 96 bytes; the layout is ABI */
   double  min_dist2, closest[3], t_min, t_first_hit;
   int64_t k_min, tri_min, k_first_hit, tri_first_hit, n_hit, n_nonfinite;
@@ -524,6 +526,59 @@ int afe_clearance_plans_engine(afe_engine *e, afe_clearance_map *m, int64_t firs
                                const double mount[4], const afe_plan_output *plans, int n_samples,
                                double radius, double max_dist, afe_path_clearance *out,
                                int64_t *n_colliding, float *kernel_ms);
+
+/* ---- swept clearance: the exact squared distance between a SEGMENT P0 -> P1 and the mesh, with the point query's
+ * contract (IEEE double, + - * / and comparisons in a stated order, no output bit depends on the hierarchy):
+ * csrc/afe_clearance.hip states the definition (SWEPT CLEARANCE), tests/swept_checker.py restates it.  Per triangle the
+ * candidates are 0: P0, 1: P1, 2: the point where the segment crosses the triangle's plane, 3/4/5: the segment against
+ * the sides AB/AC/BC; the smallest wins, the earliest among equals.  A segment of zero length is the point query, bit for
+ * bit.  A pierced triangle gives a dist2 like 1e-30, not necessarily 0.  Meant for tick-to-tick motion and the chords of a
+ * sampled path: the search bounds a segment by its axis-aligned box, which is loose for a long diagonal segment -- that
+ * costs time, never bits. */
+typedef struct afe_segment_clearance {   /* 48 bytes; the layout is ABI */
+  double  dist2;        /* +inf: no triangle within max_dist, or a non-finite coordinate */
+  double  s;            /* parameter of the closest point on the segment, P0 + (P1 - P0) * s  (NaN: none) */
+  double  closest[3];   /* the closest point on the triangle (NaN: none) */
+  int32_t tri;          /* index in the order given to afe_clearance_map_create (-1: none) */
+  int32_t kind;         /* the winning candidate, 0 .. 5 (-1: none) */
+} afe_segment_clearance;
+/* n explicit segments: p0, p1 planar [3][n] doubles; out: n records.  max_dist as afe_clearance_query.  n == 0 is AFE_OK. */
+int afe_clearance_segments(afe_clearance_map *m, int64_t n, const double *p0, const double *p1, double max_dist,
+                           afe_segment_clearance *out, float *kernel_ms);
+/* The counting build for such a batch (the records are discarded): stats[0] tree nodes visited, [1] triangle box tests,
+ * [2] double-precision segment evaluations, [3] segments. */
+int afe_clearance_segments_stats(afe_clearance_map *m, int64_t n, const double *p0, const double *p1, double max_dist,
+                                 uint64_t stats[4], float *kernel_ms);
+
+/* afe_path_clearance over CHORDS: the sample points w_k are those of afe_clearance_paths, chord k is (w_k, w_k+1) for
+ * k = 0 .. K-2, every chord is answered by the unbounded segment query.  The fields mean what they mean there, with
+ * "chord" for "sample"; a chord with a non-finite end is counted in n_nonfinite and is never a hit.  s_min and
+ * s_first_hit are the segment parameters of the closest points, t_min and t_first_hit their times
+ * t_k + (t_k+1 - t_k) * s. */
+typedef struct afe_path_sweep {          /* 8-byte members only, 112 bytes; the layout is ABI */
+  double  min_dist2, closest[3], t_min, t_first_hit;
+  int64_t k_min, tri_min, k_first_hit, tri_first_hit, n_hit, n_nonfinite;
+  double  s_min, s_first_hit;
+} afe_path_sweep;
+/* The swept siblings of afe_clearance_paths, afe_clearance_paths_stats (stats[3]: chords, n_paths * (n_samples - 1)) and
+ * afe_clearance_plans_engine: the same arguments, the same refusals, afe_path_sweep records. */
+int afe_clearance_paths_swept(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range,
+                              const double *origin, const double *rot, int n_samples, double radius, double max_dist,
+                              afe_path_sweep *out, int64_t *n_colliding, float *kernel_ms);
+int afe_clearance_paths_swept_stats(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const double *t_range,
+                                    const double *origin, const double *rot, int n_samples, double radius,
+                                    double max_dist, uint64_t stats[4], float *kernel_ms);
+int afe_clearance_plans_engine_swept(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t count,
+                                     const double mount[4], const afe_plan_output *plans, int n_samples,
+                                     double radius, double max_dist, afe_path_sweep *out,
+                                     int64_t *n_colliding, float *kernel_ms);
+/* Pure host (no GPU): an upper bound, in metres, on how far the quintic leaves the polyline of its n_samples sample
+ * points: h*h/8 * max|p''| with h = |t_end - t_begin| / (K - 1) and |p''| bounded per axis by
+ * sum_j |c_j| (5-j)(4-j) T^(3-j), T = max(|t_begin|, |t_end|), the axes combined by the Euclidean norm, times the
+ * Frobenius norm of rot9 if given, rounded up by 1 + 2^-40.  sqrt(min_dist2) of the swept audit minus this bound is a
+ * clearance the CURVE keeps.  The bound is crude (triangle inequalities throughout) and not tuned. */
+int afe_path_chord_deviation(const double *coeffs18, double t_begin, double t_end, const double *rot9, int n_samples,
+                             double *bound_m);
 
 /* ---- image truth: the planner's own self-evaluation (DepthImagePlanner.cpp:1031-1098 IsCollisionFreeGroundTruth and
  * :972-1002 MeasureConservativeness, Section IV.A of the RAPPIDS paper) --------------------------------------------
@@ -614,6 +669,15 @@ int afe_contact_monitor_get(afe_contact_monitor *c, int64_t first, int64_t count
 /* back to "nothing seen" for vehicles [first, first+count) */
 int afe_contact_monitor_reset(afe_contact_monitor *c, int64_t first, int64_t count);
 int afe_contact_monitor_destroy(afe_contact_monitor *c);   /* NULL is AFE_ERR_INVALID_ARG */
+/* The SWEPT monitor: the same handle type, served by the same _update/_get/_reset/_destroy.  It keeps every vehicle's
+ * previous world position on the device (the double the last update itself formed) and an update measures the segment
+ * from there to the current position, so an obstacle thinner than the distance flown between two updates is not missed.
+ * A vehicle's first update after creation or _reset (and after an update that found its position non-finite) measures
+ * the zero-length segment: exactly the point monitor's answer.  first_contact_us is the time of the update whose
+ * segment came within the radius.  _reset also forgets the previous position: reset the vehicles you move with
+ * afe_set_state, or the jump is measured as a flight. */
+int afe_contact_monitor_create_swept(afe_engine *e, afe_clearance_map *m, double contact_radius, double search_radius,
+                                     afe_contact_monitor **out);
 
 /* ---- ensemble statistics ---------------------------------------------------
  * What a Monte-Carlo sweep ends with: the distribution of the ensemble's state
