@@ -306,11 +306,12 @@ static void sort_doubles(double *a, int n) { /* std::sort on a handful of double
 }
 
 /* ---- Pyramid ------------------------------------------------------------- */
-typedef struct {
-  double depth;
-  int right, top, left, bottom;
-  double normal[4][3];
-} pyramid;
+typedef ora_pyramid pyramid;
+
+/* test hook: where the calling thread's next run leaves its pyramid list */
+static _Thread_local ora_pyramid *ora_pyr_sink = 0;
+static _Thread_local int ora_pyr_sink_cap = 0;
+void ora_planner_pyramids(ora_pyramid *out, int cap) { ora_pyr_sink = out; ora_pyr_sink_cap = cap; }
 
 typedef struct {
   const ora_planner_config *cfg;
@@ -809,6 +810,11 @@ void ora_planner_run(const ora_planner_config *cfg, const uint16_t *depth, const
     if (flags_out) flags_out[k] = (uint8_t)result;
   }
   out->n_pyramids = P.n_pyr;
+  if (ora_pyr_sink) {
+    if (P.n_pyr > 0 && ora_pyr_sink_cap > 0)
+      memcpy(ora_pyr_sink, P.pyr, sizeof(pyramid) * (size_t)(P.n_pyr < ora_pyr_sink_cap ? P.n_pyr : ora_pyr_sink_cap));
+    ora_pyr_sink = 0;
+  }
   free(P.pyr);
 }
 

@@ -13,11 +13,23 @@
  *              place: oracle/_ref/traj_probe -> tests/golden/planner_math_kat.json);
  *              candidate sampling against libstdc++ std::mt19937 +
  *              uniform_real_distribution in the reference's call shape.
- *   unpinned : everything that needs Vec3 / cv::Mat (RapidTrajectoryGenerator
- *              feasibility tests, monotonic sections, pyramid inflation, the
- *              search loop): restated line by line, reference quirks included
- *              (e.g. DepthImagePlanner.cpp:648 assigns bottomShrinkTemp to
- *              rightEdgeShrunk).
+ *              The whole planner -- the search loop, RapidTrajectoryGenerator's
+ *              feasibility tests, the monotonic sections, pyramid inflation
+ *              (reference quirks included, e.g. DepthImagePlanner.cpp:648
+ *              assigns bottomShrinkTemp to rightEdgeShrunk) and the order of
+ *              the pyramid list -- against the reference's own
+ *              DepthImagePlanner.cpp, RapidTrajectoryGenerator.cpp and
+ *              SingleAxisTrajectory.cpp compiled in place (oracle/_ref/
+ *              planner_probe, against the declaration-only eigen_decl and the
+ *              three-field cv::Mat of cv_decl -> tests/golden/
+ *              planner_reference.npz): ora_planner_run reproduces every
+ *              candidate's TrajectoryTestResult, the counters, the winner's
+ *              coefficients and GetPyramids() of 224 plans bit for bit
+ *              (tests/test_planner_reference.py).
+ *   unpinned : nothing of this file that the reference states.  The candidate
+ *              COUNT in place of the wall-clock budget and the two cost
+ *              functions are the caller's in the reference's design too;
+ *              ora_planner_sampled_collision is this project's own check.
  */
 #ifndef AGRIFLY_ORACLE_PLANNER_H
 #define AGRIFLY_ORACLE_PLANNER_H
@@ -85,6 +97,15 @@ void ora_planner_samples(uint32_t seed, int width, int height, int n, double (*s
  * test; this is a denser independent version, not a restatement) */
 int ora_planner_sampled_collision(const ora_planner_config *cfg, const uint16_t *depth,
                                   const double coeffs[6][3], double tf, int n_samples);
+
+/* test hook: the calling thread's NEXT ora_planner_run copies its pyramid list (GetPyramids(): sorted by depth, the
+ * reference's insertion order among equal depths) to out, at most cap entries; one run, then off again */
+typedef struct ora_pyramid {  /* Pyramid.hpp */
+  double depth;
+  int right, top, left, bottom;
+  double normal[4][3];
+} ora_pyramid;
+void ora_planner_pyramids(ora_pyramid *out, int cap);
 
 /* test hook: move the k-th acos / cos / pow result of the calling thread's next run by `ulps` (k < 0: off) */
 void ora_planner_nudge(long call_index, int ulps);

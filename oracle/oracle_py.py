@@ -378,6 +378,14 @@ class OraPlanResult(C.Structure):
                 ("n_collision_free", C.c_int), ("n_pyramids", C.c_int)]
 
 
+class OraPyramid(C.Structure):
+    _fields_ = [("depth", C.c_double), ("right", C.c_int), ("top", C.c_int), ("left", C.c_int), ("bottom", C.c_int),
+                ("normal", (C.c_double * 3) * 4)]
+
+
+PYRAMID_DTYPE = np.dtype([("depth", "<f8"), ("right", "<i4"), ("top", "<i4"), ("left", "<i4"), ("bottom", "<i4"),
+                          ("normal", "<f8", (4, 3))])
+
 _planner_bound = False
 
 
@@ -404,6 +412,8 @@ def planner_lib():
         L.ora_planner_run.argtypes = [C.POINTER(OraPlannerConfig), C.c_void_p, dp, dp, dp, C.c_void_p, C.c_int,
                                       C.POINTER(OraPlanResult), C.c_void_p]
         L.ora_planner_run.restype = None
+        L.ora_planner_pyramids.argtypes = [C.c_void_p, C.c_int]
+        L.ora_planner_pyramids.restype = None
         L.ora_planner_nudge.argtypes = [C.c_long, C.c_int]
         L.ora_planner_nudge.restype = None
         L.ora_planner_nudge_calls.argtypes = []
@@ -439,7 +449,15 @@ def planner_nudge_calls():
     return int(planner_lib().ora_planner_nudge_calls())
 
 
-def planner_run(cfg, depth, vel0, acc0, grav, samples):
+def planner_run(cfg, depth, vel0, acc0, grav, samples, want_pyramids=False):
+    """-> (result, flags), and with want_pyramids the run's pyramid list as a PYRAMID_DTYPE array (test hook)"""
+    if want_pyramids:
+        cap = 4096
+        pyr = np.zeros(cap, PYRAMID_DTYPE)
+        planner_lib().ora_planner_pyramids(pyr.ctypes.data, cap)
+        res, flags = planner_run(cfg, depth, vel0, acc0, grav, samples)
+        assert res.n_pyramids <= cap
+        return res, flags, pyr[:res.n_pyramids].copy()
     d = np.ascontiguousarray(depth, dtype=np.uint16)
     assert d.shape == (cfg.height, cfg.width)
     s = np.ascontiguousarray(samples, dtype=np.float64)

@@ -1,7 +1,9 @@
 """RAPPIDS planner: the oracle's pinned parts against the reference's own
 stand-alone sources (RootFinder.hpp, SingleAxisTrajectory.{hpp,cpp}: tests/golden/
 planner_math_kat.json), candidate sampling against libstdc++, and behavioural checks of the
-unpinned search on synthetic depth images.  CPU only."""
+search on synthetic depth images.  (The search itself -- feasibility tests, monotonic sections,
+pyramid inflation -- is pinned to the reference's own DepthImagePlanner.cpp, compiled in place, by
+tests/test_planner_reference.py.)  CPU only."""
 import ctypes as C
 import json
 import os
