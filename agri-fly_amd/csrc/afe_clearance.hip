@@ -156,6 +156,7 @@ namespace {
 
 using afe::DevBuf;
 using afe::EngineAccess;
+using afe::PinnedBuf;
 using afe::StreamTimer;
 
 constexpr int kBlock = 256;
@@ -1176,13 +1177,11 @@ struct afe_clearance_map {
   int64_t n_tri = 0, n_nodes = 0;
   int depth = 0;
   double bounds[6] = {0, 0, 0, 0, 0, 0};
-  CNode *nodes = nullptr;
-  CTri *tris = nullptr;
+  DevBuf nodes, tris;   // CNode, CTri
   ClrArgs base;         // the tree's part of the kernel arguments
   // afe_clearance_plans_engine's device scratch (plans, records, one counter), grown on demand; calls take turns on it
   std::mutex scratch_lock;
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf scratch;
 };
 
 struct afe_contact_monitor {
@@ -1191,14 +1190,11 @@ struct afe_contact_monitor {
   int64_t n = 0;
   int device = 0;
   double contact2 = 0, search2 = 0;
-  double *min_dist2 = nullptr;
-  uint64_t *first_us = nullptr;
-  int32_t *first_tri = nullptr;
-  unsigned long long *counts = nullptr;       // device, two words
-  unsigned long long *counts_host = nullptr;  // pinned, two words
-  // the swept monitor only: every vehicle's position as its last update formed it, planar [3][n], and whether there is one
-  double *prev = nullptr;
-  uint32_t *prev_valid = nullptr;
+  DevBuf min_dist2, first_us, first_tri;      // double, uint64, int32 per vehicle
+  DevBuf counts;                              // two unsigned long long
+  PinnedBuf<> counts_host;                    // the same
+  // the swept monitor only: every vehicle's position as its last update formed it, planar double [3][n], and whether there is one (uint32)
+  DevBuf prev, prev_valid;
 };
 
 namespace {
@@ -1236,12 +1232,12 @@ int query_points(afe_clearance_map *m, int64_t n_points, const double *pos, doub
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
-  if (stats && hipMemset(d_stats.p, 0, 24) != hipSuccess) return AFE_ERR_HIP;
+  if (stats && hipMemset(d_stats.get(), 0, 24) != hipSuccess) return AFE_ERR_HIP;
   ClrArgs g = m->base;
   g.max_dist2 = max_dist * max_dist;
-  g.pos = d_pos.p; g.anchor_xy = nullptr; g.stride = n_points; g.first = 0; g.count = n_points; g.elem_size = 8;
-  g.dist2_out = (double *)d_d2.p; g.tri_out = (int32_t *)d_tri.p; g.closest_out = (double *)d_cl.p; g.out_stride = n_points;
-  g.stats = (unsigned long long *)d_stats.p;
+  g.pos = d_pos.get(); g.anchor_xy = nullptr; g.stride = n_points; g.first = 0; g.count = n_points; g.elem_size = 8;
+  g.dist2_out = (double *)d_d2.get(); g.tri_out = (int32_t *)d_tri.get(); g.closest_out = (double *)d_cl.get(); g.out_stride = n_points;
+  g.stats = (unsigned long long *)d_stats.get();
   float ms = 0;
   const int rc = stats ? launch_query<false, true>(g, nullptr, &ms) : launch_query<false, false>(g, nullptr, &ms);
   if (rc != AFE_OK) return rc;
@@ -1284,15 +1280,15 @@ int query_segments(afe_clearance_map *m, int64_t n_seg, const double *p0, const 
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
-  if (stats && hipMemset(d_stats.p, 0, 24) != hipSuccess) return AFE_ERR_HIP;
+  if (stats && hipMemset(d_stats.get(), 0, 24) != hipSuccess) return AFE_ERR_HIP;
   SegArgs a;
   std::memset(&a, 0, sizeof(a));
   a.g = m->base;
   a.g.max_dist2 = max_dist * max_dist;
-  a.g.pos = d_p1.p; a.g.anchor_xy = nullptr; a.g.stride = n_seg; a.g.first = 0; a.g.count = n_seg; a.g.elem_size = 8;
-  a.g.stats = (unsigned long long *)d_stats.p;
-  a.p0 = (const double *)d_p0.p;
-  a.out = (afe_segment_clearance *)d_out.p;
+  a.g.pos = d_p1.get(); a.g.anchor_xy = nullptr; a.g.stride = n_seg; a.g.first = 0; a.g.count = n_seg; a.g.elem_size = 8;
+  a.g.stats = (unsigned long long *)d_stats.get();
+  a.p0 = (const double *)d_p0.get();
+  a.out = (afe_segment_clearance *)d_out.get();
   float ms = 0;
   const int rc = stats ? launch_swept<false, true>(a, nullptr, &ms) : launch_swept<false, false>(a, nullptr, &ms);
   if (rc != AFE_OK) return rc;
@@ -1325,16 +1321,16 @@ extern "C" int afe_clearance_map_create(int device, const float *triangles, int6
   m->depth = h.depth;
   for (int k = 0; k < 3; k++) { m->bounds[k] = h.scene.lo[k]; m->bounds[3 + k] = h.scene.hi[k]; }
   const size_t node_bytes = std::max<size_t>(h.nodes.size(), 1) * sizeof(CNode);
-  if (hipMalloc((void **)&m->nodes, node_bytes) != hipSuccess || hipMalloc((void **)&m->tris, packed.size() * sizeof(CTri)) != hipSuccess ||
-      (!h.nodes.empty() && hipMemcpy(m->nodes, h.nodes.data(), h.nodes.size() * sizeof(CNode), hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(m->tris, packed.data(), packed.size() * sizeof(CTri), hipMemcpyHostToDevice) != hipSuccess) {
+  if (!m->nodes.alloc(node_bytes) || !m->tris.alloc(packed.size() * sizeof(CTri)) ||
+      (!h.nodes.empty() && hipMemcpy(m->nodes.get(), h.nodes.data(), h.nodes.size() * sizeof(CNode), hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(m->tris.get(), packed.data(), packed.size() * sizeof(CTri), hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
     (void)afe_clearance_map_destroy(m);
     return AFE_ERR_HIP;
   }
   ClrArgs &g = m->base;
   std::memset(&g, 0, sizeof(g));
-  g.nodes = m->nodes; g.tris = m->tris;
+  g.nodes = m->nodes.as<CNode>(); g.tris = m->tris.as<CTri>();
   g.root_ref = h.root_ref;
   g.big_first = (uint32_t)h.n_small; g.n_big = (uint32_t)(n_tri - h.n_small);
   for (int k = 0; k < 3; k++) {
@@ -1349,9 +1345,6 @@ extern "C" int afe_clearance_map_destroy(afe_clearance_map *m) {
   if (!m) return AFE_ERR_INVALID_ARG;
   (void)hipSetDevice(m->device);
   (void)hipDeviceSynchronize();      // a query on some stream may still be reading the tables
-  if (m->nodes) (void)hipFree(m->nodes);
-  if (m->tris) (void)hipFree(m->tris);
-  if (m->scratch) (void)hipFree(m->scratch);
   delete m;
   return AFE_OK;
 }
@@ -1430,7 +1423,7 @@ extern "C" int afe_clearance_query_engine(afe_engine *e, afe_clearance_map *m, i
     g.dist2_out = (double *)dist2_out; g.tri_out = (int32_t *)tri_out; g.closest_out = (double *)closest_out;
   } else {
     if (!d_d2.alloc(n * 8) || !d_tri.alloc(n * 4) || (closest_out && !d_cl.alloc(n * 24))) { (void)hipGetLastError(); return AFE_ERR_HIP; }
-    g.dist2_out = (double *)d_d2.p; g.tri_out = (int32_t *)d_tri.p; g.closest_out = (double *)d_cl.p;
+    g.dist2_out = (double *)d_d2.get(); g.tri_out = (int32_t *)d_tri.get(); g.closest_out = (double *)d_cl.get();
   }
   float ms = 0;
   rc = launch_query<false, false>(g, acc.stream, &ms);     // synchronises (timing)
@@ -1486,7 +1479,7 @@ int run_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const
   const size_t n = (size_t)n_paths;
   DevBuf d_c, d_t, d_o, d_r, d_out, d_words;
   if (!d_c.upload(coeffs, n * 144) || !d_t.upload(t_range, n * 16) || (origin && !d_o.upload(origin, n * 24)) || (rot && !d_r.upload(rot, n * 72)) ||
-      !d_out.alloc(n * rec_size) || !d_words.alloc(32) || hipMemset(d_words.p, 0, 32) != hipSuccess) {
+      !d_out.alloc(n * rec_size) || !d_words.alloc(32) || hipMemset(d_words.get(), 0, 32) != hipSuccess) {
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
@@ -1495,10 +1488,10 @@ int run_paths(afe_clearance_map *m, int64_t n_paths, const double *coeffs, const
   a.t = m->base;
   a.n_paths = n_paths; a.n_samples = n_samples;
   a.radius2 = radius * radius; a.max_dist2 = max_dist * max_dist;
-  a.coeffs = (const double *)d_c.p; a.t_range = (const double *)d_t.p; a.origin = (const double *)d_o.p; a.rot = (const double *)d_r.p;
-  a.out = (afe_path_clearance *)d_out.p;
-  a.n_colliding = (unsigned long long *)d_words.p;
-  a.stats = stats ? (unsigned long long *)d_words.p + 1 : nullptr;
+  a.coeffs = (const double *)d_c.get(); a.t_range = (const double *)d_t.get(); a.origin = (const double *)d_o.get(); a.rot = (const double *)d_r.get();
+  a.out = (afe_path_clearance *)d_out.get();
+  a.n_colliding = (unsigned long long *)d_words.get();
+  a.stats = stats ? (unsigned long long *)d_words.get() + 1 : nullptr;
   float ms = 0;
   const int rc = launch_paths<false>(a, swept, nullptr, &ms);
   if (rc != AFE_OK) return rc;
@@ -1603,14 +1596,11 @@ int plans_engine(afe_engine *e, afe_clearance_map *m, int64_t first, int64_t cou
   const hipStream_t stream = acc.stream;
   const size_t n = (size_t)count, plan_bytes = n * sizeof(afe_plan_output), rec_bytes = n * (swept ? sizeof(afe_path_sweep) : sizeof(afe_path_clearance));
   std::lock_guard<std::mutex> turn(m->scratch_lock);
-  if (m->scratch_bytes < plan_bytes + rec_bytes + 8) {
+  if (m->scratch.capacity() < plan_bytes + rec_bytes + 8) {
     if (hipStreamSynchronize(stream) != hipSuccess) return AFE_ERR_HIP;
-    if (m->scratch) (void)hipFree(m->scratch);
-    m->scratch = nullptr; m->scratch_bytes = 0;
-    if (hipMalloc(&m->scratch, plan_bytes + rec_bytes + 8) != hipSuccess) { (void)hipGetLastError(); m->scratch = nullptr; return AFE_ERR_HIP; }
-    m->scratch_bytes = plan_bytes + rec_bytes + 8;
+    if (!m->scratch.alloc(plan_bytes + rec_bytes + 8)) { (void)hipGetLastError(); return AFE_ERR_HIP; }
   }
-  char *base = (char *)m->scratch;        // records | plans | counter: every part 8-byte aligned
+  char *base = m->scratch.as<char>();        // records | plans | counter: every part 8-byte aligned
   PathArgs a;
   std::memset(&a, 0, sizeof(a));
   a.t = m->base;
@@ -1661,12 +1651,12 @@ namespace {
 int monitor_reset_range(afe_contact_monitor *c, int64_t first, int64_t count, hipStream_t stream) {
   for (int64_t done = 0; done < count; done += kPointsPerLaunch) {
     const int64_t n = std::min(count - done, kPointsPerLaunch);
-    hipLaunchKernelGGL(afe_clearance_reset_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, c->min_dist2, c->first_us,
-                       c->first_tri, first + done, n);
+    hipLaunchKernelGGL(afe_clearance_reset_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, c->min_dist2.as<double>(),
+                       c->first_us.as<uint64_t>(), c->first_tri.as<int32_t>(), first + done, n);
     if (hipGetLastError() != hipSuccess) return AFE_ERR_HIP;
   }
   // the swept monitor forgets where these vehicles were: their next update is the zero-length segment
-  if (c->prev_valid && hipMemsetAsync(c->prev_valid + first, 0, (size_t)count * 4, stream) != hipSuccess) return AFE_ERR_HIP;
+  if (c->prev_valid.get() && hipMemsetAsync(c->prev_valid.as<uint32_t>() + first, 0, (size_t)count * 4, stream) != hipSuccess) return AFE_ERR_HIP;
   return AFE_OK;
 }
 }  // namespace
@@ -1684,10 +1674,8 @@ int monitor_create(afe_engine *e, afe_clearance_map *m, double contact_radius, d
   c->contact2 = contact_radius * contact_radius;
   c->search2 = search_radius * search_radius;
   const size_t n = (size_t)c->n;
-  if (hipMalloc((void **)&c->min_dist2, n * 8) != hipSuccess || hipMalloc((void **)&c->first_us, n * 8) != hipSuccess ||
-      hipMalloc((void **)&c->first_tri, n * 4) != hipSuccess || hipMalloc((void **)&c->counts, 16) != hipSuccess ||
-      hipHostMalloc((void **)&c->counts_host, 16, hipHostMallocDefault) != hipSuccess ||
-      (swept && (hipMalloc((void **)&c->prev, n * 24) != hipSuccess || hipMalloc((void **)&c->prev_valid, n * 4) != hipSuccess))) {
+  if (!c->min_dist2.alloc(n * 8) || !c->first_us.alloc(n * 8) || !c->first_tri.alloc(n * 4) || !c->counts.alloc(16) ||
+      !c->counts_host.alloc(16) || (swept && (!c->prev.alloc(n * 24) || !c->prev_valid.alloc(n * 4)))) {
     (void)hipGetLastError();
     (void)afe_contact_monitor_destroy(c);
     return AFE_ERR_HIP;
@@ -1724,24 +1712,26 @@ extern "C" int afe_contact_monitor_update(afe_contact_monitor *c, int64_t *n_in_
   ClrArgs g = c->map->base;
   g.max_dist2 = c->search2;
   g.pos = view.pos; g.anchor_xy = view.pos_anchor_xy; g.stride = view.stride; g.first = 0; g.count = c->n; g.elem_size = view.state_elem_size;
-  g.min_dist2 = c->min_dist2; g.first_us = c->first_us; g.first_tri = c->first_tri; g.counts = c->counts;
+  g.min_dist2 = c->min_dist2.as<double>(); g.first_us = c->first_us.as<uint64_t>(); g.first_tri = c->first_tri.as<int32_t>();
+  g.counts = c->counts.as<unsigned long long>();
   g.contact2 = c->contact2; g.now_us = now_us;
-  if (hipMemsetAsync(c->counts, 0, 16, stream) != hipSuccess) return AFE_ERR_HIP;
-  if (c->prev) {
+  if (hipMemsetAsync(g.counts, 0, 16, stream) != hipSuccess) return AFE_ERR_HIP;
+  if (c->prev.get()) {
     SegArgs a;
     std::memset(&a, 0, sizeof(a));
     a.g = g;
-    a.prev = c->prev; a.prev_valid = c->prev_valid; a.prev_stride = c->n;
+    a.prev = c->prev.as<double>(); a.prev_valid = c->prev_valid.as<uint32_t>(); a.prev_stride = c->n;
     rc = launch_swept<true, false>(a, stream, nullptr);
   } else {
     rc = launch_query<true, false>(g, stream, nullptr);
   }
   if (rc != AFE_OK) return rc;
   // the only bytes that cross the bus: one 16-byte copy
-  if (hipMemcpyAsync(c->counts_host, c->counts, 16, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+  const unsigned long long *counts_host = c->counts_host.as<unsigned long long>();
+  if (hipMemcpyAsync(c->counts_host.get(), g.counts, 16, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
     return AFE_ERR_HIP;
-  if (n_in_contact) *n_in_contact = (int64_t)c->counts_host[0];
-  if (n_ever_in_contact) *n_ever_in_contact = (int64_t)c->counts_host[1];
+  if (n_in_contact) *n_in_contact = (int64_t)counts_host[0];
+  if (n_ever_in_contact) *n_ever_in_contact = (int64_t)counts_host[1];
   return AFE_OK;
 }
 
@@ -1755,9 +1745,9 @@ extern "C" int afe_contact_monitor_get(afe_contact_monitor *c, int64_t first, in
   afe::engine_stream_device(c->engine, (void **)&stream, &device);
   if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return AFE_ERR_HIP;
   const size_t n = (size_t)count;
-  if ((min_dist2 && hipMemcpy(min_dist2, c->min_dist2 + first, n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (first_contact_us && hipMemcpy(first_contact_us, c->first_us + first, n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (first_contact_tri && hipMemcpy(first_contact_tri, c->first_tri + first, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+  if ((min_dist2 && hipMemcpy(min_dist2, c->min_dist2.as<double>() + first, n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (first_contact_us && hipMemcpy(first_contact_us, c->first_us.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (first_contact_tri && hipMemcpy(first_contact_tri, c->first_tri.as<int32_t>() + first, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
     return AFE_ERR_HIP;
   return AFE_OK;
 }
@@ -1777,13 +1767,6 @@ extern "C" int afe_contact_monitor_destroy(afe_contact_monitor *c) {
   if (!c) return AFE_ERR_INVALID_ARG;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  if (c->min_dist2) (void)hipFree(c->min_dist2);
-  if (c->first_us) (void)hipFree(c->first_us);
-  if (c->first_tri) (void)hipFree(c->first_tri);
-  if (c->counts) (void)hipFree(c->counts);
-  if (c->counts_host) (void)hipHostFree(c->counts_host);
-  if (c->prev) (void)hipFree(c->prev);
-  if (c->prev_valid) (void)hipFree(c->prev_valid);
   delete c;
   return AFE_OK;
 }

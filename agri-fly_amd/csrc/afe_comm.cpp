@@ -229,7 +229,7 @@ struct afe_group {
   std::vector<afe_engine *> engines;
   std::vector<int> devices;
   std::vector<int64_t> first, count;
-  std::vector<float *> all_xyz;       // per shard: planar [3][n_total] on that shard's device
+  std::vector<DevBuf> all_xyz;        // per shard: planar float [3][n_total] on that shard's device
   std::vector<hipEvent_t> packed;     // per shard: its scratch is ready
   std::vector<hipEvent_t> pulled;     // per shard: it has pulled every block it needs
   int64_t n_total = 0;
@@ -258,7 +258,7 @@ extern "C" int afe_group_create(afe_group **out, int64_t n_vehicles, int precisi
     g->devices.push_back(devices[k]);
     g->first.push_back(first);
     g->count.push_back(cnt);
-    g->all_xyz.push_back(nullptr);
+    g->all_xyz.emplace_back();
     hipEvent_t ev = nullptr;
     if (hipSetDevice(devices[k]) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { afe_group_destroy(g); return AFE_ERR_HIP; }
     g->packed.push_back(ev);
@@ -310,7 +310,7 @@ extern "C" int afe_group_destroy(afe_group *g) {
   if (!g) return AFE_ERR_INVALID_ARG;
   for (size_t k = 0; k < g->engines.size(); k++) {
     (void)hipSetDevice(g->devices[k]);
-    if (g->all_xyz[k]) (void)hipFree(g->all_xyz[k]);
+    g->all_xyz[k].reset();
     if (k < g->packed.size() && g->packed[k]) (void)hipEventDestroy(g->packed[k]);
     if (k < g->pulled.size() && g->pulled[k]) (void)hipEventDestroy(g->pulled[k]);
     if (g->engines[k]) afe_destroy(g->engines[k]);
@@ -375,7 +375,8 @@ extern "C" int afe_group_gather_positions(afe_group *g, float **dev_xyz_all_out)
     engine_stream_device(g->engines[k], &sv, &dev);
     streams[k] = (hipStream_t)sv;
     if (hipSetDevice(dev) != hipSuccess) { g->err = "hipSetDevice failed"; return AFE_ERR_HIP; }
-    if (!g->all_xyz[k] && hipMalloc((void **)&g->all_xyz[k], (size_t)g->n_total * 3 * sizeof(float)) != hipSuccess) {
+    const size_t xyz_bytes = (size_t)g->n_total * 3 * sizeof(float);
+    if (!g->all_xyz[k].reserve(xyz_bytes, xyz_bytes)) {
       g->err = "hipMalloc of the gathered-position buffer failed";
       return AFE_ERR_HIP;
     }
@@ -395,15 +396,15 @@ extern "C" int afe_group_gather_positions(afe_group *g, float **dev_xyz_all_out)
         // no direct access between the two devices (or the host asked): the runtime's peer copy, which stages through
         // host memory where it has to; contiguous rows, so one call per component
         for (int c = 0; c < 3 && err == hipSuccess; c++)
-          err = hipMemcpyPeerAsync(g->all_xyz[d] + (size_t)c * g->n_total + g->first[s], g->devices[d], scratch[s] + (size_t)c * g->count[s], g->devices[s],
+          err = hipMemcpyPeerAsync(g->all_xyz[d].as<float>() + (size_t)c * g->n_total + g->first[s], g->devices[d], scratch[s] + (size_t)c * g->count[s], g->devices[s],
                                    (size_t)g->count[s] * 4, streams[d]);
       } else {
-        err = hipMemcpy2DAsync(g->all_xyz[d] + g->first[s], (size_t)g->n_total * 4, scratch[s], (size_t)g->count[s] * 4,
+        err = hipMemcpy2DAsync(g->all_xyz[d].as<float>() + g->first[s], (size_t)g->n_total * 4, scratch[s], (size_t)g->count[s] * 4,
                                (size_t)g->count[s] * 4, 3, hipMemcpyDeviceToDevice, streams[d]);
       }
       if (err != hipSuccess) { g->err = std::string(g->staged && s != d ? "staged peer copy: " : "peer copy: ") + hipGetErrorString(err); return AFE_ERR_HIP; }
     }
-    if (dev_xyz_all_out) dev_xyz_all_out[d] = g->all_xyz[d];
+    if (dev_xyz_all_out) dev_xyz_all_out[d] = g->all_xyz[d].as<float>();
   }
   // a shard's scratch must not be repacked before every reader has pulled it: readers' streams are
   // joined back into the owner's stream

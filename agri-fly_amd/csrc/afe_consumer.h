@@ -5,7 +5,7 @@
 //   engine_stream_device / engine_device_view / engine_shard   the engine's entry points for the library's other translation
 //                        units (implemented in afe_engine.cpp; afe_world.hip and afe_comm.cpp use the first and the last alone)
 //   pick_gfx950          the device a create call runs on: the given one or the current one, refused unless it is a gfx950
-//   DevBuf               a device allocation that lives as long as its scope
+//   DevBuf / PinnedBuf   device / pinned host memory that lives as long as its owner: a scope, or a handle (afe_devmem.h)
 //   StreamTimer          two events round the launches of a call; without timing it is nothing and synchronises nothing
 //   engine_enter         the ONE way a consumer gets at the engine: stream, device and view, the device made current
 //   engine_range_bad     [first, first + count) against the engine's size, nothing touched
@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "../../include/agrifly_engine.h"
+#include "afe_devmem.h"
 
 namespace afe {
 
@@ -47,15 +48,31 @@ inline int pick_gfx950(int device, int *out) {
   return AFE_OK;
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-  bool upload(const void *src, size_t bytes) { return alloc(bytes) && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
-  bool download(void *host, size_t bytes) const { return hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+// hipMalloc / hipFree, and pinned host memory with the flags of its one kind of use (afe_devmem.h: the owner and its rules).
+// A refusal is taken off the runtime -- which keeps a thread's last error until somebody reads it -- and kept here for whoever
+// wants its text: a request granted at the second attempt (reserve's fallback) leaves no error behind for the launches after it.
+inline hipError_t &last_refusal() { static thread_local hipError_t e = hipSuccess; return e; }
+inline void *granted(hipError_t status, void *p) {
+  if (status == hipSuccess) return p;
+  (void)hipGetLastError();
+  last_refusal() = status;
+  return nullptr;
+}
+struct DeviceMemory {
+  static void *get(size_t bytes) { void *p = nullptr; return granted(hipMalloc(&p, bytes), p); }
+  static void put(void *p) { (void)hipFree(p); }
+};
+template <unsigned FLAGS>
+struct PinnedMemory {
+  static void *get(size_t bytes) { void *p = nullptr; return granted(hipHostMalloc(&p, bytes, FLAGS), p); }
+  static void put(void *p) { (void)hipHostFree(p); }
+};
+template <unsigned FLAGS = hipHostMallocDefault>
+using PinnedBuf = OwnedBuf<PinnedMemory<FLAGS>>;
+
+struct DevBuf : OwnedBuf<DeviceMemory> {
+  bool upload(const void *src, size_t bytes) { return alloc(bytes) && hipMemcpy(get(), src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
+  bool download(void *host, size_t bytes) const { return hipMemcpy(host, get(), bytes, hipMemcpyDeviceToHost) == hipSuccess; }
 };
 
 // The start event is recorded on construction; finish() goes behind the last launch.  Untimed: no event, no record, no wait.

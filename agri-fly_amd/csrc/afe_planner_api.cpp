@@ -59,22 +59,15 @@ namespace {
 // candidate sections, ...); allocating and freeing them every call costs milliseconds at 30 plans a second, so the
 // library keeps them between calls -- one set per process, grown on demand, on the device of the last call -- and
 // plan calls take turns on it (they would take turns on the GPU anyway).  afe_planner_release_scratch() gives the
-// memory back.
-struct ScratchSlot {
-  void *p = nullptr;
-  size_t cap = 0;
-};
+// memory back.  (The set is never destroyed: at the end of the process the runtime may be gone before it.)
 std::mutex g_scratch_mutex;
-ScratchSlot g_scratch[20];
+const int kScratchSlots = 20;
+DevBuf *const g_scratch = new DevBuf[kScratchSlots];
 int g_scratch_device = -1;
 
 void release_scratch_locked() {
   if (g_scratch_device >= 0) (void)hipSetDevice(g_scratch_device);
-  for (ScratchSlot &s : g_scratch) {
-    if (s.p) (void)hipFree(s.p);
-    s.p = nullptr;
-    s.cap = 0;
-  }
+  for (int k = 0; k < kScratchSlots; k++) g_scratch[k].reset();
   g_scratch_device = -1;
 }
 
@@ -83,23 +76,10 @@ struct PooledBuf {
   int slot;
   explicit PooledBuf(int slot_) : slot(slot_) {}
   bool alloc(size_t bytes) {
-    ScratchSlot &s = g_scratch[slot];
     if (bytes == 0) bytes = 1;
-    if (s.cap < bytes) {
-      if (s.p) (void)hipFree(s.p);
-      s.p = nullptr;
-      s.cap = 0;
-      const size_t want = bytes + bytes / 8;
-      if (hipMalloc(&s.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        if (hipMalloc(&s.p, bytes) != hipSuccess) { s.p = nullptr; return false; }
-        s.cap = bytes;
-      } else {
-        s.cap = want;
-      }
-    }
-    p = s.p;
-    return true;
+    const bool ok = g_scratch[slot].reserve(bytes, bytes + bytes / 8);
+    p = g_scratch[slot].get();
+    return ok;
   }
   bool upload(const void *src, size_t bytes) { return alloc(bytes) && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
 };

@@ -777,14 +777,14 @@ struct afe_scene {
   int depth = 0;
   double bounds[6] = {0, 0, 0, 0, 0, 0};
   int plain_walk_only = 0;
-  PairNode *pairs = nullptr;   // 8 x n_pairs (Builder::pairs)
+  DevBuf pairs;                // PairNode, 8 x n_pairs (Builder::pairs)
   int64_t n_pairs = 0;
-  TriRec *tris = nullptr;
-  float *tribox = nullptr;     // 8 x n_tri x 8 floats
+  DevBuf tris;                 // TriRec
+  DevBuf tribox;               // 8 x n_tri x 8 floats
   uint32_t big_first = 0, n_big = 0;   // the triangles kept out of the tree (RenderArgs)
   // pixel-ray tables, one per camera geometry this scene has been rendered with (kept until the scene goes:
   // a launch still in flight on some stream may be reading one)
-  struct RayTable { int width, height; double cx, cy, focal; double *uv; };
+  struct RayTable { int width, height; double cx, cy, focal; DevBuf uv; };
   std::vector<RayTable> ray_tables;
   // Tile-entry tables (one 64-bit word per tile group of a launch), kept and reused: a launch takes a table no launch in
   // flight is using -- `done` is recorded behind the render kernel that reads it -- or makes one.  (Round 6: the table used
@@ -794,7 +794,7 @@ struct afe_scene {
   // tables that live as long as the scene.)
   // (`taken`: a launch is being queued on it -- nobody else may have it, whatever its event says; `used`: `done` has been
   //  recorded behind a render kernel that reads it, free again once that event has completed)
-  struct EntryTable { void *p = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool used = false, taken = false; };
+  struct EntryTable { DevBuf mem; hipEvent_t done = nullptr; bool used = false, taken = false; };
   std::list<EntryTable> entry_tables;       // (a list: launches hold pointers to their table outside the lock)
   std::mutex entry_mutex;
 };
@@ -813,20 +813,20 @@ int launch_render(afe_scene *s, const afe_camera *cam, int64_t count, const doub
     const int nx = ((cam->width + kTileW - 1) / kTileW) * kTileW, ny = ((cam->height + kTileH - 1) / kTileH) * kTileH;
     const double *uv = nullptr;
     for (const afe_scene::RayTable &t : s->ray_tables)
-      if (t.width == cam->width && t.height == cam->height && t.cx == cam->cx && t.cy == cam->cy && t.focal == cam->focal_length) uv = t.uv;
+      if (t.width == cam->width && t.height == cam->height && t.cx == cam->cx && t.cy == cam->cy && t.focal == cam->focal_length) uv = t.uv.as<double>();
     if (!uv) {
-      double *fresh = nullptr;
-      if (hipMalloc((void **)&fresh, (size_t)(nx + ny) * sizeof(double)) != hipSuccess) return AFE_ERR_HIP;
-      hipLaunchKernelGGL(afe_pixel_ray_table_kernel, dim3((unsigned)((nx + ny + 255) / 256)), dim3(256), 0, stream, fresh, nx, ny,
+      DevBuf fresh;
+      if (!fresh.alloc((size_t)(nx + ny) * sizeof(double))) return AFE_ERR_HIP;
+      hipLaunchKernelGGL(afe_pixel_ray_table_kernel, dim3((unsigned)((nx + ny + 255) / 256)), dim3(256), 0, stream, fresh.as<double>(), nx, ny,
                          cam->cx, cam->cy, cam->focal_length);
       // other streams may use the table from now on: make it complete before it is published
-      if (hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(fresh); return AFE_ERR_HIP; }
-      s->ray_tables.push_back({cam->width, cam->height, cam->cx, cam->cy, cam->focal_length, fresh});
-      uv = fresh;
+      if (hipStreamSynchronize(stream) != hipSuccess) return AFE_ERR_HIP;
+      uv = fresh.as<double>();
+      s->ray_tables.push_back({cam->width, cam->height, cam->cx, cam->cy, cam->focal_length, std::move(fresh)});
     }
     r.uv = uv;
   }
-  r.pairs = s->pairs; r.n_pairs = s->n_pairs; r.tris = s->tris; r.tribox = s->tribox; r.n_tri = s->n_tri; r.counters = dev_counters;
+  r.pairs = s->pairs.as<PairNode>(); r.n_pairs = s->n_pairs; r.tris = s->tris.as<TriRec>(); r.tribox = s->tribox.as<float>(); r.n_tri = s->n_tri; r.counters = dev_counters;
   r.big_first = s->big_first; r.n_big = s->n_big; r.entry = nullptr;
   r.width = cam->width; r.height = cam->height;
   r.tiles_x = (cam->width + kTileW - 1) / kTileW;
@@ -863,21 +863,19 @@ int launch_render(afe_scene *s, const afe_camera *cam, int64_t count, const doub
         const size_t need = (size_t)n_groups * sizeof(uint64_t);
         std::lock_guard<std::mutex> lock(s->entry_mutex);
         for (afe_scene::EntryTable &t : s->entry_tables)
-          if (t.bytes >= need && !t.taken && (!t.used || hipEventQuery(t.done) == hipSuccess)) { table = &t; break; }
+          if (t.mem.capacity() >= need && !t.taken && (!t.used || hipEventQuery(t.done) == hipSuccess)) { table = &t; break; }
         if (!table) {
           afe_scene::EntryTable t;
-          if (hipMalloc(&t.p, need + need / 4) != hipSuccess || hipEventCreateWithFlags(&t.done, hipEventDisableTiming) != hipSuccess) {
+          if (!t.mem.alloc(need + need / 4) || hipEventCreateWithFlags(&t.done, hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
-            if (t.p) (void)hipFree(t.p);
             rc = AFE_ERR_HIP;
             break;
           }
-          t.bytes = need + need / 4;
-          s->entry_tables.push_back(t);
+          s->entry_tables.push_back(std::move(t));
           table = &s->entry_tables.back();
         }
         table->taken = true;                             // ours until the event behind our render kernel is recorded (below)
-        entry = (uint64_t *)table->p;
+        entry = table->mem.as<uint64_t>();
       }
       r.entry = nullptr;
       hipLaunchKernelGGL(afe_tile_entry_kernel, dim3((unsigned)((n_groups + 63) / 64)), dim3(64), 0, stream, r, entry, cull_big);
@@ -1024,12 +1022,11 @@ extern "C" int afe_scene_create(int device, const float *triangles, int64_t n_tr
         B[2 * k + 1] = mirrored ? -src[2 * k] : src[2 * k + 1];
       }
     }
-  if (hipMalloc((void **)&s->pairs, pairs.size() * sizeof(PairNode)) != hipSuccess ||
-      hipMalloc((void **)&s->tribox, tribox.size() * sizeof(float)) != hipSuccess ||
-      hipMemcpy(s->tribox, tribox.data(), tribox.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc((void **)&s->tris, packed.size() * sizeof(TriRec)) != hipSuccess ||
-      hipMemcpy(s->pairs, pairs.data(), pairs.size() * sizeof(PairNode), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s->tris, packed.data(), packed.size() * sizeof(TriRec), hipMemcpyHostToDevice) != hipSuccess) {
+  if (!s->pairs.alloc(pairs.size() * sizeof(PairNode)) ||
+      !s->tribox.upload(tribox.data(), tribox.size() * sizeof(float)) ||
+      !s->tris.alloc(packed.size() * sizeof(TriRec)) ||
+      hipMemcpy(s->pairs.get(), pairs.data(), pairs.size() * sizeof(PairNode), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(s->tris.get(), packed.data(), packed.size() * sizeof(TriRec), hipMemcpyHostToDevice) != hipSuccess) {
     afe_scene_destroy(s);
     return AFE_ERR_HIP;
   }
@@ -1136,11 +1133,7 @@ extern "C" int afe_scene_check_hierarchy(const float *triangles, int64_t n_tri, 
 
 extern "C" void afe_scene_destroy(afe_scene *s) {
   if (!s) return;
-  for (const afe_scene::RayTable &t : s->ray_tables) (void)hipFree(t.uv);
-  for (afe_scene::EntryTable &t : s->entry_tables) { if (t.done) { (void)hipEventSynchronize(t.done); (void)hipEventDestroy(t.done); } if (t.p) (void)hipFree(t.p); }
-  if (s->pairs) (void)hipFree(s->pairs);
-  if (s->tris) (void)hipFree(s->tris);
-  if (s->tribox) (void)hipFree(s->tribox);
+  for (afe_scene::EntryTable &t : s->entry_tables) if (t.done) { (void)hipEventSynchronize(t.done); (void)hipEventDestroy(t.done); }
   delete s;
 }
 
@@ -1169,10 +1162,10 @@ extern "C" int afe_render_depth(afe_scene *s, const afe_camera *cam, int64_t n_v
   if (!d_pos.upload(pos, (size_t)n_views * 24) || !d_att.upload(att, (size_t)n_views * 32) ||
       !d_pose.alloc((size_t)n_views * 96) || !d_out.alloc((size_t)n_views * px * 2))
     return AFE_ERR_HIP;
-  int rc = launch_poses(d_pos.p, nullptr, d_att.p, n_views, 0, n_views, 8, mount, (double *)d_pose.p, nullptr);
+  int rc = launch_poses(d_pos.get(), nullptr, d_att.get(), n_views, 0, n_views, 8, mount, (double *)d_pose.get(), nullptr);
   if (rc != AFE_OK) return rc;
   float ms = 0;
-  rc = launch_render(s, cam, n_views, (const double *)d_pose.p, (uint16_t *)d_out.p, nullptr, &ms);
+  rc = launch_render(s, cam, n_views, (const double *)d_pose.get(), (uint16_t *)d_out.get(), nullptr, &ms);
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
   if (!d_out.download(depth_out, (size_t)n_views * px * 2)) return AFE_ERR_HIP;
@@ -1192,12 +1185,12 @@ extern "C" int afe_render_depth_stats(afe_scene *s, const afe_camera *cam, int64
   if (!d_pos.upload(pos, (size_t)n_views * 24) || !d_att.upload(att, (size_t)n_views * 32) ||
       !d_pose.alloc((size_t)n_views * 96) || !d_out.alloc((size_t)n_views * px * 2) || !d_cnt.alloc(64))
     return AFE_ERR_HIP;
-  if (hipMemset(d_cnt.p, 0, 64) != hipSuccess) return AFE_ERR_HIP;
-  int rc = launch_poses(d_pos.p, nullptr, d_att.p, n_views, 0, n_views, 8, mount, (double *)d_pose.p, nullptr);
+  if (hipMemset(d_cnt.get(), 0, 64) != hipSuccess) return AFE_ERR_HIP;
+  int rc = launch_poses(d_pos.get(), nullptr, d_att.get(), n_views, 0, n_views, 8, mount, (double *)d_pose.get(), nullptr);
   if (rc != AFE_OK) return rc;
   float ms = 0;
-  rc = launch_render(s, cam, n_views, (const double *)d_pose.p, (uint16_t *)d_out.p, nullptr, &ms,
-                     (unsigned long long *)d_cnt.p);
+  rc = launch_render(s, cam, n_views, (const double *)d_pose.get(), (uint16_t *)d_out.get(), nullptr, &ms,
+                     (unsigned long long *)d_cnt.get());
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
   unsigned long long host[8];
@@ -1224,13 +1217,13 @@ extern "C" int afe_render_depth_engine(afe_engine *e, afe_scene *s, const afe_ca
   uint16_t *out_dev = (uint16_t *)depth_out;
   if (!out_is_device) {
     if (!d_out.alloc((size_t)count * px * 2)) return AFE_ERR_HIP;
-    out_dev = (uint16_t *)d_out.p;
+    out_dev = (uint16_t *)d_out.get();
   }
-  rc = launch_poses(view.pos, view.pos_anchor_xy, view.att, view.stride, first, count, view.state_elem_size, mount, (double *)d_pose.p,
+  rc = launch_poses(view.pos, view.pos_anchor_xy, view.att, view.stride, first, count, view.state_elem_size, mount, (double *)d_pose.get(),
                     stream);
   if (rc != AFE_OK) return rc;
   float ms = 0;
-  rc = launch_render(s, cam, count, (const double *)d_pose.p, out_dev, stream, &ms);  // synchronises (timing)
+  rc = launch_render(s, cam, count, (const double *)d_pose.get(), out_dev, stream, &ms);  // synchronises (timing)
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
   if (!out_is_device && hipMemcpy(depth_out, out_dev, (size_t)count * px * 2, hipMemcpyDeviceToHost) != hipSuccess)

@@ -396,12 +396,11 @@ struct afe_stats_monitor {
   int n_groups = 0, n_edges = 0;
   int64_t n_chunks = 0;
   uint64_t n_updates = 0;
-  void *arena = nullptr;            // one allocation: reference, latches, tables, partials
+  afe::DevBuf arena;                // one allocation: reference, latches, tables, partials
   StatsArgs args;                   // the monitor's part of the kernel arguments
   double *hist_e2 = nullptr;        // device, kMaxHistEdges doubles
-  unsigned char *result = nullptr;       // device: n_groups records, then the histogram
-  unsigned char *result_host = nullptr;  // pinned, the same
-  size_t result_bytes = 0;
+  afe::DevBuf result;               // n_groups records, then the histogram
+  afe::PinnedBuf<> result_host;     // the same
 };
 
 namespace {
@@ -438,15 +437,10 @@ int launch_init(const StatsArgs &g, int elem, int64_t first, int64_t count, int 
 
 int alloc_result(afe_stats_monitor *m, int n_edges) {
   const size_t bytes = (size_t)m->n_groups * sizeof(afe_group_stats) + (n_edges ? (size_t)m->n_groups * (n_edges + 1) * 8 : 0);
-  if (bytes <= m->result_bytes) return AFE_OK;
-  if (m->result) (void)hipFree(m->result);
-  if (m->result_host) (void)hipHostFree(m->result_host);
-  m->result = nullptr; m->result_host = nullptr; m->result_bytes = 0;
-  if (hipMalloc((void **)&m->result, bytes) != hipSuccess || hipHostMalloc((void **)&m->result_host, bytes, hipHostMallocDefault) != hipSuccess) {
+  if (!m->result.reserve(bytes, bytes) || !m->result_host.reserve(bytes, bytes)) {
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
-  m->result_bytes = bytes;
   return AFE_OK;
 }
 
@@ -490,8 +484,8 @@ extern "C" int afe_stats_create(afe_engine *e, const int64_t *edges, int n_group
   const size_t o_gc0 = off; off += up256(NG * 8);
   const size_t o_part = off; off += up256(NC * kWords * 8);
   const size_t o_e2 = off; off += up256(kMaxHistEdges * 8);
-  bool ok = hipMalloc(&m->arena, off) == hipSuccess;
-  unsigned char *A = (unsigned char *)m->arena;
+  bool ok = m->arena.alloc(off);
+  unsigned char *A = m->arena.as<unsigned char>();
   std::memset(&m->args, 0, sizeof(m->args));
   StatsArgs &g = m->args;
   if (ok) {
@@ -525,9 +519,6 @@ extern "C" int afe_stats_destroy(afe_stats_monitor *m) {
   if (!m) return AFE_ERR_INVALID_ARG;
   (void)hipSetDevice(m->device);
   (void)hipDeviceSynchronize();
-  if (m->arena) (void)hipFree(m->arena);
-  if (m->result) (void)hipFree(m->result);
-  if (m->result_host) (void)hipHostFree(m->result_host);
   delete m;
   return AFE_OK;
 }
@@ -593,8 +584,8 @@ extern "C" int afe_stats_update(afe_stats_monitor *m, afe_group_stats *groups_ou
   const size_t hist_bytes = m->n_edges ? (size_t)m->n_groups * (m->n_edges + 1) * 8 : 0;
   g.now_us = now_us;
   g.n_edges = m->n_edges;
-  g.groups_out = (afe_group_stats *)m->result;
-  g.hist = (unsigned long long *)(m->result + rec_bytes);
+  g.groups_out = m->result.as<afe_group_stats>();
+  g.hist = (unsigned long long *)(m->result.as<unsigned char>() + rec_bytes);
   if (hist_bytes && hipMemsetAsync(g.hist, 0, hist_bytes, stream) != hipSuccess) return AFE_ERR_HIP;
   for (int64_t done = 0; done < m->n_chunks; done += kChunksPerLaunch) {
     const int64_t nc = std::min(m->n_chunks - done, kChunksPerLaunch);
@@ -606,12 +597,12 @@ extern "C" int afe_stats_update(afe_stats_monitor *m, afe_group_stats *groups_ou
   hipLaunchKernelGGL(afe_stats_group_kernel, dim3((unsigned)m->n_groups), dim3(kBlock), 0, stream, g);
   if (hipGetLastError() != hipSuccess) return AFE_ERR_HIP;
   // the only bytes that cross the bus: the group records and the histogram, one copy
-  if (hipMemcpyAsync(m->result_host, m->result, rec_bytes + hist_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+  if (hipMemcpyAsync(m->result_host.get(), m->result.get(), rec_bytes + hist_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
     return AFE_ERR_HIP;
   m->n_updates++;
-  std::memcpy(groups_out, m->result_host, rec_bytes);
-  if (hist_out) std::memcpy(hist_out, m->result_host + rec_bytes, hist_bytes);
+  std::memcpy(groups_out, m->result_host.get(), rec_bytes);
+  if (hist_out) std::memcpy(hist_out, m->result_host.as<unsigned char>() + rec_bytes, hist_bytes);
   return AFE_OK;
 }
 

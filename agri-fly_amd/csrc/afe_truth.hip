@@ -375,12 +375,12 @@ bool images_upload(const afe_planner_config *cfg, const ImageSource &s, int64_t 
     g.images = (const uint16_t *)s.images;
   } else {
     if (!d_img.upload(s.images, (size_t)s.n_images * cfg->width * cfg->height * 2)) return false;
-    g.images = (const uint16_t *)d_img.p;
+    g.images = (const uint16_t *)d_img.get();
   }
   g.image_index = nullptr;
   if (s.image_index) {
     if (!d_idx.upload(s.image_index, (size_t)n_owners * 4)) return false;
-    g.image_index = (const int32_t *)d_idx.p;
+    g.image_index = (const int32_t *)d_idx.get();
   }
   return true;
 }
@@ -421,12 +421,12 @@ int truth_records(int device, const afe_planner_config *cfg, int64_t n, const Im
   DevBuf d_img, d_idx, d_co, d_tr, d_plans, d_out, d_words;
   if (!images_upload(cfg, src, n, d_img, d_idx, g)) { (void)hipGetLastError(); return AFE_ERR_HIP; }
   bool ok = plans ? d_plans.upload(plans, (size_t)n * sizeof(afe_plan_output)) : (d_co.upload(coeffs, (size_t)n * 144) && d_tr.upload(t_range, (size_t)n * 16));
-  ok = ok && (!out || d_out.alloc((size_t)n * sizeof(afe_image_truth))) && d_words.alloc(32) && hipMemset(d_words.p, 0, 32) == hipSuccess;
+  ok = ok && (!out || d_out.alloc((size_t)n * sizeof(afe_image_truth))) && d_words.alloc(32) && hipMemset(d_words.get(), 0, 32) == hipSuccess;
   if (!ok) { (void)hipGetLastError(); return AFE_ERR_HIP; }
-  g.coeffs = (const double *)d_co.p; g.t_range = (const double *)d_tr.p; g.plans = (const afe_plan_output *)d_plans.p;
-  g.out = (afe_image_truth *)d_out.p;
-  g.n_free = (unsigned long long *)d_words.p;
-  g.stats = stats ? (unsigned long long *)d_words.p + 1 : nullptr;
+  g.coeffs = (const double *)d_co.get(); g.t_range = (const double *)d_tr.get(); g.plans = (const afe_plan_output *)d_plans.get();
+  g.out = (afe_image_truth *)d_out.get();
+  g.n_free = (unsigned long long *)d_words.get();
+  g.stats = stats ? (unsigned long long *)d_words.get() + 1 : nullptr;
 
   float ms = 0;
   StreamTimer timer(nullptr, true);
@@ -523,23 +523,23 @@ extern "C" int afe_image_truth_candidates(int device, const afe_planner_config *
   if (!images_upload(cfg, src, n, d_img, d_idx, g)) { (void)hipGetLastError(); return AFE_ERR_HIP; }
   if (!d_v.upload(vel0, (size_t)n * 24) || !d_a.upload(acc0, (size_t)n * 24) || !d_s.upload(samples, (size_t)n_tables * n_candidates * 32) ||
       (sample_table && !d_t.upload(sample_table, (size_t)n * 4)) || !d_flags.upload(flags, total) || !d_verdict.alloc(total) ||
-      (coeffs_out && !d_co.alloc(total * 144)) || !d_tally.alloc(48) || hipMemset(d_tally.p, 0, 48) != hipSuccess ||
+      (coeffs_out && !d_co.alloc(total * 144)) || !d_tally.alloc(48) || hipMemset(d_tally.get(), 0, 48) != hipSuccess ||
       (per_planner && !d_per.alloc((size_t)n * 48))) {
     (void)hipGetLastError();
     return AFE_ERR_HIP;
   }
-  g.vel0 = (const double *)d_v.p; g.acc0 = (const double *)d_a.p; g.samples = (const double *)d_s.p;
-  g.sample_table = sample_table ? (const int32_t *)d_t.p : nullptr;
-  g.verdict_out = (uint8_t *)d_verdict.p;
-  g.coeffs_out = (double *)d_co.p;
+  g.vel0 = (const double *)d_v.get(); g.acc0 = (const double *)d_a.get(); g.samples = (const double *)d_s.get();
+  g.sample_table = sample_table ? (const int32_t *)d_t.get() : nullptr;
+  g.verdict_out = (uint8_t *)d_verdict.get();
+  g.coeffs_out = (double *)d_co.get();
 
   float ms = 0;
   StreamTimer timer(nullptr, true);
   if (!timer.ok()) return AFE_ERR_HIP;
   rc = truth_launch<MODE_CANDS>(g, false, nullptr);
   if (rc == AFE_OK) {
-    hipLaunchKernelGGL(afe_truth_tally_kernel, dim3((unsigned)n), dim3(64), 0, nullptr, (const uint8_t *)d_flags.p, (const uint8_t *)d_verdict.p, n,
-                       n_candidates, (unsigned long long *)d_tally.p, (int64_t *)d_per.p);
+    hipLaunchKernelGGL(afe_truth_tally_kernel, dim3((unsigned)n), dim3(64), 0, nullptr, (const uint8_t *)d_flags.get(), (const uint8_t *)d_verdict.get(), n,
+                       n_candidates, (unsigned long long *)d_tally.get(), (int64_t *)d_per.get());
     rc = hipGetLastError() == hipSuccess ? AFE_OK : AFE_ERR_HIP;
   }
   rc = timer.finish(rc, &ms);

@@ -580,18 +580,15 @@ using namespace afe;
 
 struct afe_world {
   int device = 0;
-  int64_t cap_points = 0;      // capacity of the per-point scratch
-  int64_t cap_cells = 0;       // capacity of the per-cell scratch (cells + 1 dead bin + 1 end)
-  uint32_t *counts = nullptr;  // per cell, becomes the exclusive scan (starts)
-  uint32_t *block_sums = nullptr;
-  uint32_t *cell = nullptr, *slot = nullptr;
-  uint4 *sorted = nullptr;
-  int32_t *leftover = nullptr;
-  uint64_t *leftover_keys = nullptr;   // per listed query: packed (distance, index) minimum of the brute force
-  int *lohi = nullptr;         // 6 ints + leftover counter [6], the explicit brute force's count [7], the query's count for the launch behind it [8]
-  BoundsPartial *bounds_part = nullptr;   // one record per workgroup of the bounds kernel
-  int64_t cap_self = 0;
-  float *self_scratch = nullptr;
+  // device scratch (ensure_capacity); every buffer knows its own size, so one that a refused growth emptied is asked for again
+  DevBuf counts;               // uint32 per cell (cells + 1 dead bin + 1 end), becomes the exclusive scan (starts)
+  DevBuf block_sums;           // uint32
+  DevBuf cell, slot;           // uint32 per point
+  DevBuf sorted;               // uint4 per point
+  DevBuf leftover;             // int32 per point
+  DevBuf leftover_keys;        // uint64 per listed query: packed (distance, index) minimum of the brute force
+  DevBuf lohi;                 // 6 ints + leftover counter [6], the explicit brute force's count [7], the query's count for the launch behind it [8]
+  DevBuf bounds_part;          // one BoundsPartial per workgroup of the bounds kernel
   GridDesc grid = {};
   int64_t grid_n_all = -1;      // ensemble size the grid shape was chosen for
   int64_t grid_first = -1, grid_n_self = -1;   // and the block of it the queries were for
@@ -602,11 +599,12 @@ struct afe_world {
   // stopping rule allows for how far anybody has moved since the sort
   int resort_every = 1;         // sort every this many queries (1: always)
   int since_sort = 0;
-  bool sort_valid = false;
-  float *ref = nullptr;         // [3][cap_points]: positions at the last sort, original order
-  uint32_t *words = nullptr;    // device: [0] bound on the movement since the sort (float bits)
-  uint32_t *tickets = nullptr;  // device: last_workgroup counters of the regather launch, of the query launch, of the brute-force launch behind it
-  uint32_t *host_flag = nullptr;   // pinned: [0] a kernel asks for a new sort, [1] queries the last finished query's rings left over (informational)
+  bool sort_stale = true;       // no sort yet, or a per-point array has been replaced since (ensure_capacity), or a regather asked
+  DevBuf ref;                   // float [3][ref_stride()]: positions at the last sort, original order
+  int64_t ref_stride() const { return (int64_t)(ref.capacity() / (3 * sizeof(float))); }
+  DevBuf words;                 // uint32: [0] bound on the movement since the sort (float bits)
+  DevBuf tickets;               // uint32: last_workgroup counters of the regather launch, of the query launch, of the brute-force launch behind it
+  PinnedBuf<hipHostMallocCoherent | hipHostMallocMapped> host_flag;   // uint32: [0] a kernel asks for a new sort, [1] queries the last finished query's rings left over (informational)
   std::string err;
 };
 
@@ -622,17 +620,11 @@ int wfail(afe_world *w, int status, const std::string &m) {
     hipError_t err__ = (call);                                                                         \
     if (err__ != hipSuccess) return wfail((w), AFE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(err__)); \
   } while (0)
-
-void free_points(afe_world *w) {
-  if (w->cell) (void)hipFree(w->cell);
-  if (w->slot) (void)hipFree(w->slot);
-  if (w->sorted) (void)hipFree(w->sorted);
-  if (w->ref) (void)hipFree(w->ref);
-  w->ref = nullptr; w->sort_valid = false;
-  if (w->leftover) (void)hipFree(w->leftover);
-  if (w->leftover_keys) (void)hipFree(w->leftover_keys);
-  w->cell = w->slot = nullptr; w->sorted = nullptr; w->leftover = nullptr; w->leftover_keys = nullptr;
-}
+// a buffer of the world's asks for memory (afe_devmem.h); the refusal's code is kept by the policy (afe_consumer.h)
+#define W_MEM(w, hip_call, request)                                                                    \
+  do {                                                                                                 \
+    if (!(w)->request) return wfail((w), AFE_ERR_HIP, std::string(#hip_call " for " #request ": ") + hipGetErrorString(last_refusal())); \
+  } while (0)
 
 // The grid covers the CORE of the ensemble: the bounding box cut to mean +- 6 sigma per axis.  Points
 // outside it are clamped into its boundary cells -- clamping never increases a cell distance, so
@@ -700,32 +692,29 @@ void choose_grid(const float lo[3], const float hi[3], const double stats[7], in
   }
 }
 
+// Room for n_all points and n_cells_total cells, with headroom.  Every array answers for itself: one that a refused growth
+// left empty is asked for again by the next call, whatever became of the others.  A per-point array that is replaced takes
+// the cell order of the last sort with it (sort_stale).
 int ensure_capacity(afe_world *w, int64_t n_all, int64_t n_cells_total) {
-  if (n_all > w->cap_points) {
-    free_points(w);
-    const int64_t cap = n_all + n_all / 8 + 1024;
-    W_HIP(w, hipMalloc((void **)&w->cell, (size_t)cap * 4));
-    W_HIP(w, hipMalloc((void **)&w->slot, (size_t)cap * 4));
-    W_HIP(w, hipMalloc((void **)&w->sorted, (size_t)cap * sizeof(uint4)));
-    W_HIP(w, hipMalloc((void **)&w->ref, (size_t)cap * 3 * sizeof(float)));
-    W_HIP(w, hipMalloc((void **)&w->leftover, (size_t)cap * 4));
-    W_HIP(w, hipMalloc((void **)&w->leftover_keys, (size_t)cap * 8));
-    w->cap_points = cap;
+  const size_t n = (size_t)n_all, cap = (size_t)(n_all + n_all / 8 + 1024);
+  W_MEM(w, hipMalloc, cell.reserve(n * 4, cap * 4, &w->sort_stale));
+  W_MEM(w, hipMalloc, slot.reserve(n * 4, cap * 4, &w->sort_stale));
+  W_MEM(w, hipMalloc, sorted.reserve(n * sizeof(uint4), cap * sizeof(uint4), &w->sort_stale));
+  W_MEM(w, hipMalloc, ref.reserve(n * 3 * sizeof(float), cap * 3 * sizeof(float), &w->sort_stale));
+  W_MEM(w, hipMalloc, leftover.reserve(n * 4, cap * 4, &w->sort_stale));
+  W_MEM(w, hipMalloc, leftover_keys.reserve(n * 8, cap * 8, &w->sort_stale));
+  if (n_cells_total > 0) {   // (0: a query's first call, before the grid is shaped, and the explicit brute force, which sorts nothing)
+    const size_t m = (size_t)n_cells_total;
+    bool replaced = false;
+    W_MEM(w, hipMalloc, counts.reserve(m * 4, (m + 4096) * 4, &replaced));
+    // one partial sum per 1024 cells of what `counts` holds, and one more: replaced with it
+    if (replaced || !w->block_sums.get()) W_MEM(w, hipMalloc, block_sums.alloc(((w->counts.capacity() / 4 + 1023) / 1024 + 1) * 4));
   }
-  if (n_cells_total > w->cap_cells) {
-    if (w->counts) (void)hipFree(w->counts);
-    if (w->block_sums) (void)hipFree(w->block_sums);
-    w->counts = w->block_sums = nullptr;
-    const int64_t cap = n_cells_total + 4096;
-    W_HIP(w, hipMalloc((void **)&w->counts, (size_t)cap * 4));
-    W_HIP(w, hipMalloc((void **)&w->block_sums, (size_t)((cap + 1023) / 1024 + 1) * 4));
-    w->cap_cells = cap;
-  }
-  if (!w->lohi) W_HIP(w, hipMalloc((void **)&w->lohi, 16 * sizeof(int)));
-  if (!w->words) { W_HIP(w, hipMalloc((void **)&w->words, 4 * sizeof(uint32_t))); W_HIP(w, hipMemset(w->words, 0, 4 * sizeof(uint32_t))); }
-  if (!w->tickets) { W_HIP(w, hipMalloc((void **)&w->tickets, 3 * AFE_WORLD_TICKET_WORDS * sizeof(uint32_t))); W_HIP(w, hipMemset(w->tickets, 0, 3 * AFE_WORLD_TICKET_WORDS * sizeof(uint32_t))); }
-  if (!w->host_flag) { W_HIP(w, hipHostMalloc((void **)&w->host_flag, 64, hipHostMallocCoherent | hipHostMallocMapped)); w->host_flag[0] = 0; w->host_flag[1] = 0; }
-  if (!w->bounds_part) W_HIP(w, hipMalloc((void **)&w->bounds_part, AFE_WORLD_BOUNDS_BLOCKS * sizeof(BoundsPartial)));
+  if (!w->lohi.get()) W_MEM(w, hipMalloc, lohi.alloc(16 * sizeof(int)));
+  if (!w->words.get()) { W_MEM(w, hipMalloc, words.alloc(4 * sizeof(uint32_t))); W_HIP(w, hipMemset(w->words.get(), 0, 4 * sizeof(uint32_t))); }
+  if (!w->tickets.get()) { W_MEM(w, hipMalloc, tickets.alloc(3 * AFE_WORLD_TICKET_WORDS * sizeof(uint32_t))); W_HIP(w, hipMemset(w->tickets.get(), 0, 3 * AFE_WORLD_TICKET_WORDS * sizeof(uint32_t))); }
+  if (!w->host_flag.get()) { W_MEM(w, hipHostMalloc, host_flag.alloc(64)); w->host_flag.as<uint32_t>()[0] = 0; w->host_flag.as<uint32_t>()[1] = 0; }
+  if (!w->bounds_part.get()) W_MEM(w, hipMalloc, bounds_part.alloc(AFE_WORLD_BOUNDS_BLOCKS * sizeof(BoundsPartial)));
   return AFE_OK;
 }
 
@@ -747,16 +736,7 @@ int afe::world_create(int device, afe_world **out) {
 void afe::world_destroy(afe_world *w) {
   if (!w) return;
   (void)hipSetDevice(w->device);
-  free_points(w);
-  if (w->counts) (void)hipFree(w->counts);
-  if (w->block_sums) (void)hipFree(w->block_sums);
-  if (w->lohi) (void)hipFree(w->lohi);
-  if (w->bounds_part) (void)hipFree(w->bounds_part);
-  if (w->self_scratch) (void)hipFree(w->self_scratch);
-  if (w->words) (void)hipFree(w->words);
-  if (w->tickets) (void)hipFree(w->tickets);
-  if (w->host_flag) (void)hipHostFree(w->host_flag);
-  delete w;
+  delete w;      // (its buffers go back with it)
 }
 
 const char *afe::world_last_error(const afe_world *w) { return w ? w->err.c_str() : "null world"; }
@@ -783,9 +763,9 @@ int afe::world_nearest(afe_world *w, void *hip_stream, const float *all_xyz, int
                        w->grid_cell_arg != cell_size || w->since_refresh + 1 >= w->refresh_every;
   if (reshape) {
     hipLaunchKernelGGL(world_bounds_kernel, dim3(AFE_WORLD_BOUNDS_BLOCKS), dim3(256), 0, st, all_xyz, n_all, sharded ? first_global : (int64_t)0,
-                       sharded ? n_self : n_all, w->bounds_part);
+                       sharded ? n_self : n_all, w->bounds_part.as<BoundsPartial>());
     static thread_local BoundsPartial host_part[AFE_WORLD_BOUNDS_BLOCKS];
-    W_HIP(w, hipMemcpyAsync(host_part, w->bounds_part, sizeof(host_part), hipMemcpyDeviceToHost, st));
+    W_HIP(w, hipMemcpyAsync(host_part, w->bounds_part.get(), sizeof(host_part), hipMemcpyDeviceToHost, st));
     W_HIP(w, hipStreamSynchronize(st));
     int lohi[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
     double stats[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -810,43 +790,47 @@ int afe::world_nearest(afe_world *w, void *hip_stream, const float *all_xyz, int
   }
   const GridDesc g = w->grid;
   const int64_t m = g.n_cells + 2;   // cells, the dead bin, and the end sentinel
-  const int64_t cap_before = w->cap_points;
   if ((rc = ensure_capacity(w, n_all, m))) return rc;
   const unsigned pb = (unsigned)((n_all + 255) / 256);
-  if (*(volatile uint32_t *)w->host_flag) { w->sort_valid = false; *(volatile uint32_t *)w->host_flag = 0; }   // a regather met a vehicle the sort never listed
-  const bool keep_order = !reshape && w->sort_valid && cap_before == w->cap_points && w->since_sort + 1 < w->resort_every;
+  uint32_t *const cell = w->cell.as<uint32_t>(), *const slot = w->slot.as<uint32_t>(), *const counts = w->counts.as<uint32_t>();
+  uint32_t *const block_sums = w->block_sums.as<uint32_t>(), *const words = w->words.as<uint32_t>(), *const tickets = w->tickets.as<uint32_t>();
+  uint32_t *const host_flag = w->host_flag.as<uint32_t>(), *const lohi = w->lohi.as<uint32_t>();
+  uint4 *const sorted = w->sorted.as<uint4>();
+  float *const ref = w->ref.as<float>();
+  if (*(volatile uint32_t *)host_flag) { w->sort_stale = true; *(volatile uint32_t *)host_flag = 0; }   // a regather met a vehicle the sort never listed
+  const bool keep_order = !reshape && !w->sort_stale && w->since_sort + 1 < w->resort_every;
   if (keep_order) {
     // 2'. the cell order of the last sort, today's positions (vehicles move centimetres between two queries, cells are
     // metres wide): one pass instead of the five of a sort
     w->since_sort++;
     // (the partial maxima live in the leftover-key scratch: the brute force behind the query is the next to touch it)
-    float *partial = (float *)w->leftover_keys;
-    hipLaunchKernelGGL(world_regather_kernel, dim3(pb), dim3(256), 0, st, all_xyz, n_all, w->cell, w->slot, w->ref, w->cap_points, w->sorted, partial,
-                       (uint32_t *)(w->lohi + 6), w->words, w->host_flag, w->tickets);
+    float *partial = w->leftover_keys.as<float>();
+    hipLaunchKernelGGL(world_regather_kernel, dim3(pb), dim3(256), 0, st, all_xyz, n_all, cell, slot, ref, w->ref_stride(), sorted, partial,
+                       lohi + 6, words, host_flag, tickets);
   } else {
     // 2. counting sort by cell
-    W_HIP(w, hipMemsetAsync(w->counts, 0, (size_t)m * 4, st));
-    hipLaunchKernelGGL(world_count_kernel, dim3(pb), dim3(256), 0, st, all_xyz, n_all, g, w->counts, w->cell, w->slot, (uint32_t *)(w->lohi + 6), w->words);
+    W_HIP(w, hipMemsetAsync(counts, 0, (size_t)m * 4, st));
+    hipLaunchKernelGGL(world_count_kernel, dim3(pb), dim3(256), 0, st, all_xyz, n_all, g, counts, cell, slot, lohi + 6, words);
     const int64_t nb = (m + 1023) / 1024;
-    hipLaunchKernelGGL(world_scan_local_kernel, dim3((unsigned)nb), dim3(256), 0, st, w->counts, w->counts, w->block_sums, m);
-    hipLaunchKernelGGL(world_scan_blocks_kernel, dim3(1), dim3(256), 0, st, w->block_sums, nb);
-    hipLaunchKernelGGL(world_scan_add_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w->counts, w->block_sums, m);
-    hipLaunchKernelGGL(world_scatter_kernel, dim3(pb), dim3(256), 0, st, all_xyz, n_all, w->counts, w->cell, w->slot, w->sorted, w->ref, w->cap_points);
-    w->sort_valid = true;
+    hipLaunchKernelGGL(world_scan_local_kernel, dim3((unsigned)nb), dim3(256), 0, st, counts, counts, block_sums, m);
+    hipLaunchKernelGGL(world_scan_blocks_kernel, dim3(1), dim3(256), 0, st, block_sums, nb);
+    hipLaunchKernelGGL(world_scan_add_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, counts, block_sums, m);
+    hipLaunchKernelGGL(world_scatter_kernel, dim3(pb), dim3(256), 0, st, all_xyz, n_all, counts, cell, slot, sorted, ref, w->ref_stride());
+    w->sort_stale = false;
     w->since_sort = 0;
   }
   // 3. queries in cell order; isolated vehicles finish in the brute-force kernel
-  uint32_t *left_count = (uint32_t *)(w->lohi + 6);
+  uint32_t *left_count = lohi + 6;
   // What the rings leave over is finished by the brute force: inside the query launch by its last workgroup while that is
   // little work (AFE_WORLD_TAIL_WORK distance evaluations: nothing or next to nothing left over in a small world), by the launch behind it otherwise,
   // which shares (query, chunk of the ensemble) items over the whole device and leaves at once when its count is zero.
   // No host-side guess is involved: a world that suddenly leaves 10^5 queries over (a fleet scattered beyond the grid's
   // rings) is answered in milliseconds by that launch, not in seconds by one compute unit.
-  uint32_t *big_count = (uint32_t *)(w->lohi + 8);
-  hipLaunchKernelGGL(world_query_kernel, dim3(pb), dim3(256), 0, st, w->sorted, n_all, w->counts, g, first_global, n_self, dist2_out,
-                     index_out, left_count, w->leftover, w->leftover_keys, w->words, all_xyz, big_count, w->host_flag + 1, w->tickets);
-  hipLaunchKernelGGL(world_brute_chunks_kernel, dim3(1024), dim3(256), 0, st, all_xyz, n_all, w->leftover, big_count, first_global,
-                     (unsigned long long *)w->leftover_keys, w->tickets + 2 * AFE_WORLD_TICKET_WORDS, dist2_out, index_out);
+  uint32_t *big_count = lohi + 8;
+  hipLaunchKernelGGL(world_query_kernel, dim3(pb), dim3(256), 0, st, sorted, n_all, counts, g, first_global, n_self, dist2_out,
+                     index_out, left_count, w->leftover.as<int32_t>(), w->leftover_keys.as<uint64_t>(), words, all_xyz, big_count, host_flag + 1, tickets);
+  hipLaunchKernelGGL(world_brute_chunks_kernel, dim3(1024), dim3(256), 0, st, all_xyz, n_all, w->leftover.as<int32_t>(), big_count, first_global,
+                     w->leftover_keys.as<unsigned long long>(), tickets + 2 * AFE_WORLD_TICKET_WORDS, dist2_out, index_out);
   W_HIP(w, hipGetLastError());
   return AFE_OK;
 }
@@ -867,8 +851,8 @@ int afe::world_grid_info(const afe_world *w, int dims[3], float *cell_size, int6
   if (!w) return AFE_ERR_INVALID_ARG;
   if (n_bruteforce) {   // how many queries of the last call the rings could not settle (synchronises)
     uint32_t left = 0;
-    if (!w->lohi || hipSetDevice(w->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(&left, w->lohi + 6, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!w->lohi.get() || hipSetDevice(w->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(&left, w->lohi.as<uint32_t>() + 6, 4, hipMemcpyDeviceToHost) != hipSuccess)
       return AFE_ERR_HIP;
     *n_bruteforce = left;
   }
@@ -889,13 +873,13 @@ int afe::world_nearest_bruteforce(afe_world *w, void *hip_stream, const float *a
   int rc = ensure_capacity(w, n_queries, 0);
   if (rc) return rc;
   const uint32_t nq = (uint32_t)n_queries;
-  uint32_t *cnt = (uint32_t *)(w->lohi + 7);
+  uint32_t *cnt = w->lohi.as<uint32_t>() + 7;
   W_HIP(w, hipMemcpyAsync(cnt, &nq, 4, hipMemcpyHostToDevice, st));
   W_HIP(w, hipStreamSynchronize(st));   // nq lives on this stack frame
-  hipLaunchKernelGGL(world_brute_init_kernel, dim3(64), dim3(256), 0, st, w->leftover_keys, cnt);
+  hipLaunchKernelGGL(world_brute_init_kernel, dim3(64), dim3(256), 0, st, w->leftover_keys.as<uint64_t>(), cnt);
   hipLaunchKernelGGL(world_brute_chunks_kernel, dim3(2048), dim3(256), 0, st, all_xyz, n_all, dev_queries, cnt, first_global,
-                     (unsigned long long *)w->leftover_keys, (uint32_t *)nullptr, (float *)nullptr, (int32_t *)nullptr);
-  hipLaunchKernelGGL(world_brute_finish_kernel, dim3(64), dim3(256), 0, st, dev_queries, cnt, w->leftover_keys, dist2_out, index_out);
+                     w->leftover_keys.as<unsigned long long>(), (uint32_t *)nullptr, (float *)nullptr, (int32_t *)nullptr);
+  hipLaunchKernelGGL(world_brute_finish_kernel, dim3(64), dim3(256), 0, st, dev_queries, cnt, w->leftover_keys.as<uint64_t>(), dist2_out, index_out);
   W_HIP(w, hipGetLastError());
   return AFE_OK;
 }
@@ -917,11 +901,10 @@ struct afe_uwb_network {
   double add_noise_std = 0, outlier_prob = 0, outlier_std = 0;   // UWBNetwork.cpp:15-17
   // device scratch
   int device = -1;
-  int64_t cap = 0;
-  int32_t *d_req = nullptr, *d_res = nullptr;
-  double *d_noise = nullptr;
-  uint8_t *d_out = nullptr;
-  float *d_range = nullptr;
+  DevBuf d_req, d_res;   // int32 per pair
+  DevBuf d_noise;        // double
+  DevBuf d_out;          // uint8
+  DevBuf d_range;        // float
   std::vector<double> noise;
   std::vector<uint8_t> outlier;
 };
@@ -935,14 +918,7 @@ extern "C" int afe_uwb_create(afe_uwb_network **out) {
 }
 extern "C" void afe_uwb_destroy(afe_uwb_network *u) {
   if (!u) return;
-  if (u->device >= 0) {
-    (void)hipSetDevice(u->device);
-    if (u->d_req) (void)hipFree(u->d_req);
-    if (u->d_res) (void)hipFree(u->d_res);
-    if (u->d_noise) (void)hipFree(u->d_noise);
-    if (u->d_out) (void)hipFree(u->d_out);
-    if (u->d_range) (void)hipFree(u->d_range);
-  }
+  if (u->device >= 0) (void)hipSetDevice(u->device);
   delete u;
 }
 extern "C" int afe_uwb_set_noise(afe_uwb_network *u, double noise_std_dev, double outlier_probability, double outlier_std_dev) {
@@ -980,32 +956,22 @@ extern "C" int afe_uwb_range(afe_uwb_network *u, afe_engine *e, const float *dev
   if (u->device >= 0 && u->device != device) return AFE_ERR_INVALID_ARG;
   if (hipSetDevice(device) != hipSuccess) return AFE_ERR_NO_DEVICE;
   u->device = device;
-  if (n_pairs > u->cap) {
-    if (u->d_req) (void)hipFree(u->d_req);
-    if (u->d_res) (void)hipFree(u->d_res);
-    if (u->d_noise) (void)hipFree(u->d_noise);
-    if (u->d_out) (void)hipFree(u->d_out);
-    if (u->d_range) (void)hipFree(u->d_range);
-    u->d_req = u->d_res = nullptr; u->d_noise = nullptr; u->d_out = nullptr; u->d_range = nullptr; u->cap = 0;
-    const size_t cap = (size_t)n_pairs + 1024;
-    if (hipMalloc((void **)&u->d_req, cap * 4) != hipSuccess || hipMalloc((void **)&u->d_res, cap * 4) != hipSuccess ||
-        hipMalloc((void **)&u->d_noise, cap * 8) != hipSuccess || hipMalloc((void **)&u->d_out, cap) != hipSuccess ||
-        hipMalloc((void **)&u->d_range, cap * 4) != hipSuccess)
-      return AFE_ERR_HIP;
-    u->cap = (int64_t)cap;
-  }
+  const size_t np = (size_t)n_pairs, cap = np + 1024;
+  if (!u->d_req.reserve(np * 4, cap * 4) || !u->d_res.reserve(np * 4, cap * 4) || !u->d_noise.reserve(np * 8, cap * 8) ||
+      !u->d_out.reserve(np, cap) || !u->d_range.reserve(np * 4, cap * 4))
+    return AFE_ERR_HIP;
   u->noise.resize((size_t)n_pairs);
   u->outlier.resize((size_t)n_pairs);
   afe_uwb_draw(u, n_pairs, u->noise.data(), u->outlier.data());
   hipStream_t st = (hipStream_t)stream_v;
-  if (hipMemcpyAsync(u->d_req, requester, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(u->d_res, responder, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(u->d_noise, u->noise.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(u->d_out, u->outlier.data(), (size_t)n_pairs, hipMemcpyHostToDevice, st) != hipSuccess)
+  if (hipMemcpyAsync(u->d_req.get(), requester, np * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(u->d_res.get(), responder, np * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(u->d_noise.get(), u->noise.data(), np * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(u->d_out.get(), u->outlier.data(), np, hipMemcpyHostToDevice, st) != hipSuccess)
     return AFE_ERR_HIP;
-  hipLaunchKernelGGL(world_uwb_range_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, dev_all_xyz, n_all, u->d_req,
-                     u->d_res, u->d_noise, u->d_out, n_pairs, u->d_range);
-  if (hipMemcpyAsync(range_out, u->d_range, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+  hipLaunchKernelGGL(world_uwb_range_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, dev_all_xyz, n_all, u->d_req.as<int32_t>(),
+                     u->d_res.as<int32_t>(), u->d_noise.as<double>(), u->d_out.as<uint8_t>(), n_pairs, u->d_range.as<float>());
+  if (hipMemcpyAsync(range_out, u->d_range.get(), np * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return AFE_ERR_HIP;
   if (outlier_out) std::memcpy(outlier_out, u->outlier.data(), (size_t)n_pairs);
