@@ -8,16 +8,27 @@
  * never falls back to this code.
  *
  * PARITY STATUS (see DESIGN.md "Oracle"):
- *   - rigid body, motors, Vec3/Rotation math:
- *     **parity unpinned**.  The reference ships no tests or golden vectors and
- *     its sources for this path include <Eigen/Dense>, which this image lacks,
- *     so the reference cannot be built here without stand-ins.  The functions
- *     below restate the reference source line by line (citations given) in
- *     the same operation order, in double, no FMA contraction.  Informational
- *     (tests/test_reference_anchors.py): flown in the reference's config-1
- *     loop they reproduce, to all nine printed digits, the positions SURVEY.md
- *     Appendix B records for the unmodified reference after 1 s and after
- *     10 s of flight (10 000 steps).
+ *   - rigid body: **pinned** to the reference's own
+ *     Quadcopter_T.cpp and Motor.cpp compiled in place (oracle/_ref/
+ *     rigid_body_probe, against the storage-only oracle/eigen_store: element
+ *     access and constants, no arithmetic).  ora_step_batch driven by
+ *     ora_clock_run equals tests/golden/rigid_body_reference.npz bit for bit:
+ *     96 vehicles, every field, the IMU floats and their noise, every
+ *     checkpoint (tests/test_rigid_body_reference.py).  Pinned with no
+ *     condition for a power-of-two diagonal inertia; pinned GIVEN THE INVERSE
+ *     for the shipped types' diagonals and full tensors: inertiaMatrix.inverse()
+ *     (Quadcopter_T.cpp:20), the path's one Eigen operation, is injected into
+ *     the probe from ora_params_init and bounded apart against the exact
+ *     inverse.  Unpinned: the bits of Eigen's own inverse() (Eigen is not in
+ *     this image), a non-identity IMU mount inside Run() (every shipped type
+ *     mounts at identity), rotor speeds other than 0 at the start (the
+ *     reference has no setter).
+ *   - motors, Rotation math (a4, a5): pinned bit for bit to Motor.cpp and
+ *     Rotation.hpp (oracle/_ref/motion_probe, tests/golden/motion_kat.json).
+ *     Informational (tests/test_reference_anchors.py): flown in the
+ *     reference's config-1 loop the functions below reproduce, to all nine
+ *     printed digits, the positions SURVEY.md Appendix B records for the
+ *     unmodified reference after 1 s and after 10 s of flight (10 000 steps).
  *   - clock / logic-gate cadence (a6): pinned against the reference's own
  *     Timer/ManualTimer headers, which compile stand-alone (oracle/_ref/
  *     timer_probe, fixture tests/golden/timer_cadence.json).

@@ -7,8 +7,17 @@
  * TEST INFRASTRUCTURE ONLY (same rules as agrifly_oracle.h).
  * PARITY STATUS: the second-order low-pass is pinned against the reference's
  * own Common/Common/Math/LowPassFilterSecondOrder.hpp (stand-alone header,
- * oracle/_ref/lpf_probe, tests/golden/lpf_kat.json); controller, mixer and the
- * call sequence are **parity unpinned** restatements (their headers need Eigen).
+ * oracle/_ref/lpf_probe, tests/golden/lpf_kat.json); the controller, the mixer,
+ * the low-pass on a Vec3f and the type constants are pinned IN CLOSED LOOP against
+ * the reference's own QuadcopterAngularVelocityController.hpp, QuadcopterMixer.hpp,
+ * LowPassFilterSecondOrder.hpp and QuadcopterConstants.hpp (they use Eigen for
+ * storage only) composed inside the reference's Quadcopter_T::Run (oracle/_ref/
+ * rigid_body_probe, tests/golden/rigid_body_closed_loop.npz: ClosedLoopBatch
+ * equals the recording bit for bit, tests/test_rigid_body_reference.py).  The
+ * call sequence between them -- the first IMU call initialises only, thrust_norm
+ * * mass, idle until a rates command arrives -- stays **parity unpinned**:
+ * QuadcopterLogic.cpp and KalmanFilter6DOF.cpp do Eigen arithmetic and are not
+ * built, and the probe's glue is the same reading of them as this file's.
  */
 #ifndef AGRIFLY_ORACLE_LOGIC_H
 #define AGRIFLY_ORACLE_LOGIC_H

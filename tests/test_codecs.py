@@ -1,9 +1,12 @@
 """Wire formats either side of the step, through the C ABI.
 Telemetry is pinned against the reference's own TelemetryPacket.hpp (compiled in
-place by oracle/_ref/telemetry_probe -> tests/golden/telemetry_kat.json); the
-radio codec (RadioTypes.hpp needs Eigen through Vec3.hpp: unbuildable here) is a
-restatement checked against a second, independent restatement in numpy
-(tests/offboard_stub.py) and hand-derived byte patterns.  CPU only."""
+place by oracle/_ref/telemetry_probe -> tests/golden/telemetry_kat.json), and so
+is the radio codec: RadioTypes.hpp only INCLUDES Eigen through Vec3.hpp and does
+no Eigen arithmetic, so it compiles in place against the declaration-only
+oracle/eigen_decl (oracle/_ref/radio_probe -> tests/golden/radio_kat.json).  Both
+restatements -- afe_radio_* behind the C ABI and the numpy one in
+tests/offboard_stub.py -- are held to those recorded answers byte for byte and
+float for float, and to each other on random values.  CPU only."""
 import ctypes as C
 import json
 import os
@@ -102,6 +105,69 @@ def test_radio_other_message_types(afa):
         m = afa.radio_decode(raw)
         assert m.type == t and m.flags == 0x80
     assert L.afe_radio_create_simple_command(5, 0, raw.ctypes.data) == 1
+
+
+def _f32(bits):
+    return np.array(bits, np.uint32).view(np.float32)
+
+
+def _same_floats(a, b):
+    """bit for bit, except that any NaN equals any NaN"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
+
+
+def test_radio_codec_against_reference_known_answers(afa, golden_dir):
+    """tests/golden/radio_kat.json, recorded from the reference's own RadioTypes.hpp: afe_radio_create_* must write the
+    recorded 23 bytes (into a zeroed buffer, as the probe did), afe_radio_decode must give the recorded type, flags and
+    floats (every field that kind of message carries) for the recorded bytes -- arbitrary ones included -- and tests/offboard_stub.radio_quantise the recorded float
+    of every field a message writes."""
+    kat = json.load(open(os.path.join(golden_dir, "radio_kat.json")))
+    L = afa.library()
+    seen, n_neg_half, n_nan = set(), 0, 0
+    for c in kat["cases"]:
+        want_raw = np.frombuffer(bytes.fromhex(c["raw"]), np.uint8)
+        assert len(want_raw) == afa.RADIO_PACKET_SIZE == 23
+        op = c["op"]
+        seen.add(op)
+        raw = np.zeros(23, np.uint8)
+        if op != "D":
+            f = np.ascontiguousarray(_f32(c["in"]))
+            if op == "R":
+                raw = np.asarray(afa.radio_create_rates_command(c["flags"], f[0], f[1:4]), np.uint8)
+            elif op == "P":
+                p, v, a = f[0:3].copy(), f[3:6].copy(), f[6:9].copy()
+                assert L.afe_radio_create_position_command(c["flags"], p.ctypes.data, v.ctypes.data, a.ctypes.data, raw.ctypes.data) == 0
+            elif op == "A":
+                a = f[0:3].copy()
+                assert L.afe_radio_create_acceleration_command(c["flags"], a.ctypes.data, C.c_float(f[3]), raw.ctypes.data) == 0
+            else:
+                assert L.afe_radio_create_simple_command({"K": 2, "I": 6}[op], c["flags"], raw.ctypes.data) == 0
+            np.testing.assert_array_equal(raw, want_raw, err_msg=str(c))
+            if op in kat["limits"]:
+                lims = kat["limits"][op]
+                for j, lim in enumerate(lims):
+                    assert _same_floats(radio_quantise(f[j:j + 1], lim), _f32(c["floats"][j:j + 1])), (c, j)
+                n_nan += int(np.isnan(f).any())
+                scaled = np.nan_to_num(f[:len(lims)].astype(np.float64), posinf=0, neginf=0) * 32768 / np.array(lims) + 0.5
+                n_neg_half += int(np.any((scaled < 0) & (np.abs(scaled - np.round(scaled)) < 1e-3)))
+        m = afa.radio_decode(want_raw)
+        assert (m.type, m.flags) == (c["type"], c["dflags"]), c
+        assert len(c["floats"]) == {3: 9, 4: 4}.get(c["type"], 10)      # the reference leaves the others uninitialised
+        assert _same_floats(list(m.floats)[:len(c["floats"])], _f32(c["floats"])), (c, list(m.floats))
+    assert seen == {"R", "P", "A", "K", "I", "D"} and n_neg_half >= 6 and n_nan >= 3
+
+
+def test_radio_known_answers_are_what_the_probe_writes_now(golden_dir):
+    """staleness (needs oracle/_ref/radio_probe, built where the reference is present)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_radio_kat", os.path.join(golden_dir, "make_radio_kat.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    if not os.path.exists(mod.PROBE):
+        pytest.skip("oracle/_ref/radio_probe not built (the reference sources are not on this machine)")
+    with open(mod.FIXTURE) as f:
+        assert f.read() == mod.dumps(mod.make_radio_kat())
 
 
 def test_cpp_delay_line_matches_reference_communications_delay(golden_dir):
