@@ -1151,6 +1151,9 @@ extern "C" int afe_destroy(afe_engine *e) {
       return AFE_ERR_HIP;
     }
   }
+  // Before anything is freed: a caller's stream (afe_set_stream) may still hold this engine's steps and consumers.  It is
+  // waited for here and said so -- not left to hipFree's wait for the whole device -- and it is the caller's to destroy.
+  if (e->stream != e->own_stream) (void)hipStreamSynchronize(e->stream);
   if (e->p_dev) (void)hipFree(e->p_dev);
   if (e->p_host) (void)hipHostFree(e->p_host);
   if (e->side_stream) (void)hipStreamSynchronize(e->side_stream);
@@ -1177,6 +1180,11 @@ extern "C" const char *afe_last_error(const afe_engine *e) { return e ? e->err.c
 
 extern "C" int afe_set_stream(afe_engine *e, void *hip_stream) {
   if (!e) return AFE_ERR_INVALID_ARG;
+  // NULL restores the engine's own stream, so the default stream cannot be meant by its handle; HIP's reserved handles for
+  // it are refused, nothing touched: the engine records events on its stream and makes its other streams wait for them
+  // (split steps, the asynchronous query, afe_event_record), which the runtime does not take with a reserved handle.
+  if ((hipStream_t)hip_stream == hipStreamLegacy || (hipStream_t)hip_stream == hipStreamPerThread)
+    return fail(e, AFE_ERR_INVALID_ARG, "the default stream (hipStreamLegacy, hipStreamPerThread) is not supported as a caller's stream: use a stream of your own");
   const int rc = main_stream(e);                     // (joins the side stream first)
   if (rc) return rc;
   AFE_HIP(e, hipStreamSynchronize(e->stream));

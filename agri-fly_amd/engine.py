@@ -1256,7 +1256,12 @@ class Ensemble:
                                            float(sigma_acc), int(seed_policy)))
 
     def set_stream(self, hip_stream):
-        self._ck(self._L.afe_set_stream(self._h, C.c_void_p(hip_stream or None)))
+        """afe_set_stream: all engine work goes to the caller's HIP stream `hip_stream` (an integer handle, e.g.
+        torch.cuda.Stream().cuda_stream), which must stay alive until the engine is closed or taken off it again.
+        None or 0 restores the engine's OWN stream -- torch's default stream has handle 0 and is NOT meant by it.  The
+        default stream is not supported as a caller's stream (HIP's reserved handles 1 and 2 are refused): queue the
+        host's work on a torch.cuda.Stream() of its own.  See the header for what is ordered."""
+        self._ck(self._L.afe_set_stream(self._h, C.c_void_p(int(hip_stream) if hip_stream else None)))
 
     # -- state ------------------------------------------------------------
     def set_state(self, pos=None, vel=None, att=None, ang_vel=None, motor_speed=None,

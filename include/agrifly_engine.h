@@ -144,8 +144,40 @@ int afe_has_dev_hooks(void);
  * against the argument table of every instantiation in the gfx950 code object inside the library. */
 int afe_persistent_kernarg_layout(int precision, int32_t offsets[4], int32_t sizes[4], int32_t *segment_bytes);
 
-/* Use a caller-owned HIP stream (hipStream_t) for all engine work, e.g.
- * torch's current stream.  NULL restores the engine's own stream. */
+/* Use a caller-owned HIP stream (hipStream_t) for all engine work, e.g. a torch.cuda.Stream()'s .cuda_stream, so that
+ * the engine's work is part of the host's own stream and needs no synchronisation against it.
+ *   What is ordered.  From the return of this call every entry point that takes the engine queues on that stream, in
+ *     call order, with whatever the host queues there itself: afe_step's launches, the setters' and getters' copies,
+ *     afe_pack_positions, afe_gather_positions, afe_event_record, the neighbour queries, afe_uwb_range, and the
+ *     library's consumers of the engine's state -- depth camera (afe_render_depth_engine), clearance query and plan
+ *     audits (afe_clearance_*_engine*), contact monitor, statistics -- which fetch the stream at every call.  Work the
+ *     host queued before an engine call is seen by it (a buffer filled on the stream and queried at once); work the host
+ *     queues after afe_step has returned sees the stepped slabs (afe_get_device_view): order at return.
+ *     afe_nearest_neighbour_async runs on a stream of the engine's own that is ordered behind the caller's stream at
+ *     the call; its results are the host's after afe_query_sync, as on the engine's own stream.
+ *   The exception.  afe_set_split_stepping(e, 2) keeps half of every step on a second stream of the engine's: the
+ *     caller's stream is then ordered behind the steps only at the NEXT engine call that touches device state or the
+ *     stream (see there) -- put afe_event_record or afe_sync between afe_step and the host's own reader.  The automatic
+ *     split (parts = 0) never engages on a caller's stream, nor do the resident grid and the engine's own queue: on a
+ *     caller's stream afe_step is the launches, whatever step mode is set (afe_persistent_running stays 0).  Same bits.
+ *   Not engine-bound.  Entry points that take a device, a scene or a map, not an engine -- afe_rappids_plan*,
+ *     afe_image_truth_*, afe_render_depth, afe_clearance_query / _segments / _paths*, afe_device_upload / _download --
+ *     are NOT moved by this call: they run on the device's default (NULL) stream, which does not wait for non-blocking
+ *     streams such as torch's.  A host that produced device input for one of them (afe_rappids_plan_device's images,
+ *     afe_image_truth_*'s with images_on_device, afe_device_download's source) on a stream of its own synchronises that
+ *     stream (hipStreamSynchronize, or an event) before the call; their results are complete at return.
+ *   Handle 0.  NULL restores the engine's own stream -- it does NOT mean the default stream, although the default
+ *     stream's handle is 0 (torch.cuda.default_stream().cuda_stream == 0): work a host queues on the default stream is
+ *     not ordered against an engine that was given 0.  The default stream is NOT SUPPORTED as a caller's stream: HIP's
+ *     reserved handles for it, hipStreamLegacy ((hipStream_t)1) and hipStreamPerThread ((hipStream_t)2), are refused
+ *     with AFE_ERR_INVALID_ARG and the engine stays where it was (the engine records events on its stream and makes
+ *     its other streams wait for them; the runtime does not take that with a reserved handle).  A host uses a stream
+ *     of its own (torch.cuda.Stream()) and queues there what the engine is to be ordered with.
+ *   Switching.  The call returns after everything queued on the old stream (a pending half of a split step, a
+ *     resident grid's last step) has finished, so nothing of the engine's is left on a stream it has given up.
+ *   Lifetime.  The stream stays the caller's: the library never destroys it.  It must outlive the engine, or the
+ *     afe_set_stream(e, NULL) (or another stream) that takes the engine off it; afe_destroy waits for it before it frees
+ *     the slabs.  NULL engine: AFE_ERR_INVALID_ARG. */
 int afe_set_stream(afe_engine *e, void *hip_stream);
 
 /* ---- configuration ------------------------------------------------------ */

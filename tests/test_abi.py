@@ -75,6 +75,15 @@ def test_plan_ticks_argument_checks(afa):
     assert ticks.tolist() == [0] * 5 and el == 0
 
 
+def test_set_stream_refuses_a_null_engine(afa):
+    """afe_set_stream without an engine is AFE_ERR_INVALID_ARG whatever the stream: NULL ("restore the engine's own"), HIP's
+    reserved handles for the default stream (hipStreamLegacy 1, hipStreamPerThread 2: refused with an engine too,
+    tests/test_gpu_caller_stream.py), any other handle"""
+    L = afa.library()
+    for handle in (None, 1, 2, 0x1000):
+        assert L.afe_set_stream(None, C.c_void_p(handle)) == 1, handle
+
+
 def test_no_device_means_loud_failure_not_fallback(afa):
     import torch
     if torch.cuda.is_available():
