@@ -61,6 +61,7 @@ from .engine import (  # noqa: F401
     camera_default_mount,
     library,
     library_path,
+    low_battery_threshold_from_type,
     params_from_type,
     path_chord_deviation,
     path_sample_points,

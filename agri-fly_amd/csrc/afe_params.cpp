@@ -272,6 +272,20 @@ extern "C" int afe_type_from_id(unsigned id) {
   }
 }
 
+extern "C" int afe_low_battery_threshold_from_type(int quadcopter_type, float *volts) {
+  if (!volts) return AFE_ERR_INVALID_ARG;
+  const float per_cell_low_voltage = 3.0f;  // QuadcopterConstants.hpp:50
+  switch (quadcopter_type) {
+    case 0: *volts = 0.0f; return AFE_OK;                       // :51, "invalid"
+    case 1: *volts = 1 * per_cell_low_voltage; return AFE_OK;   // :83
+    case 2: *volts = 1 * per_cell_low_voltage; return AFE_OK;   // :117
+    case 3: *volts = 1 * per_cell_low_voltage; return AFE_OK;   // :150
+    case 4: *volts = 3 * per_cell_low_voltage; return AFE_OK;   // :180
+    case 5: *volts = 2 * per_cell_low_voltage; return AFE_OK;   // :220
+    default: return AFE_ERR_INVALID_ARG;
+  }
+}
+
 extern "C" int afe_plan_ticks(double logic_period_s, uint64_t *elapsed_us, uint64_t dt_us,
                               int n_steps, uint8_t *tick_out) {
   if (!elapsed_us || n_steps < 0 || (n_steps > 0 && !tick_out)) return AFE_ERR_INVALID_ARG;

@@ -60,6 +60,7 @@ ABI_FUNCTIONS = [
     "afe_stats_set_histogram", "afe_stats_update", "afe_stats_get", "afe_stats_reset",
     "afe_image_truth_sample_times", "afe_image_truth_paths", "afe_image_truth_paths_stats", "afe_image_truth_plans",
     "afe_image_truth_candidates", "afe_device_upload",
+    "afe_low_battery_threshold_from_type",
 ]
 
 
@@ -261,6 +262,7 @@ def library():
     sig = {
         "afe_params_from_type": [ci, C.POINTER(VehicleParams)],
         "afe_type_from_id": [C.c_uint],
+        "afe_low_battery_threshold_from_type": [ci, C.POINTER(C.c_float)],
         "afe_create": [C.POINTER(vp), i64, ci, ci, i64],
         "afe_create_host_visible": [C.POINTER(vp), i64, ci, ci, i64],
         "afe_destroy": [eng],
@@ -446,6 +448,15 @@ def rates_logic_params_from_type(quadcopter_type):
     if rc:
         raise AfeError(rc, "invalid quadcopter type %r" % (quadcopter_type,))
     return p
+
+
+def low_battery_threshold_from_type(quadcopter_type):
+    """QuadcopterConstants(type).lowBatteryThreshold [V] as a numpy float32; types 0..5"""
+    v = C.c_float()
+    rc = library().afe_low_battery_threshold_from_type(int(quadcopter_type), C.byref(v))
+    if rc:
+        raise AfeError(rc, "invalid quadcopter type %r" % (quadcopter_type,))
+    return np.float32(v.value)
 
 
 def radio_create_rates_command(flags, thrust, ang_vel):

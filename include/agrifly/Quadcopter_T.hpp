@@ -37,6 +37,9 @@
 
 #include "../agrifly_engine.h"
 #include "SimulationObject6DOF.hpp"   // the tree's own header under AGRIFLY_USE_REFERENCE_TYPES
+#ifdef AGRIFLY_USE_REFERENCE_TYPES
+#include "Components/Logic/QuadcopterConstants.hpp"   // as the tree's Quadcopter_T.hpp:10 does
+#endif
 
 namespace agrifly {
 
@@ -85,6 +88,36 @@ inline afe_vehicle_params MakeParams(double mass, const Matrix33 &inertiaMatrix,
   return p;
 }
 
+// What the reference's constructor reads from Onboard::QuadcopterConstants(quadcopterType) and not from its argument list
+// (Quadcopter_T.cpp:70-80): the low-battery threshold behind _battVoltage and the IMU mount angles behind _R_inverse.
+// Needs no engine: inside the agri-fly tree the tree's own table is asked, outside it the engine library's
+// (afe_low_battery_threshold_from_type, pure host) and the mount of the shipped types, which is zero for every one
+// (QuadcopterConstants.hpp:60-62, 97-99, 133-135, 163-165, 202-204, 244-246).  A type the table refuses gives 0 V, as the
+// reference's `lowBatteryThreshold = 0.0f; // invalid` does (:51); nothing aborts.
+struct TypeDerived {
+  float lowBatteryThreshold;   // [V]
+  float imuYaw, imuPitch, imuRoll;   // [rad]
+};
+template <class QuadcopterTypeT>
+inline TypeDerived DeriveFromType(QuadcopterTypeT quadcopterType) {
+  TypeDerived d;
+#ifdef AGRIFLY_USE_REFERENCE_TYPES
+  Onboard::QuadcopterConstants consts((Onboard::QuadcopterConstants::QuadcopterType)quadcopterType);   // Quadcopter_T.cpp:71
+  d.lowBatteryThreshold = consts.lowBatteryThreshold;
+  d.imuYaw = consts.IMU_yaw; d.imuPitch = consts.IMU_pitch; d.imuRoll = consts.IMU_roll;   // :75-77
+#else
+  d.lowBatteryThreshold = 0.0f;
+  if (afe_low_battery_threshold_from_type(int(quadcopterType), &d.lowBatteryThreshold) != AFE_OK) d.lowBatteryThreshold = 0.0f;
+  d.imuYaw = d.imuPitch = d.imuRoll = 0.0f;
+#endif
+  return d;
+}
+// The voltage the logic is handed at every tick (Quadcopter_T.cpp:72, 163) for a threshold.
+inline float BatteryVoltage(float lowBatteryThreshold) { return 1.2f * lowBatteryThreshold; }
+// "argument not given" for the constructor's trailing overrides: a NaN, so that an explicit 0 stays an explicit 0
+inline float FromType() { return __builtin_nanf(""); }
+inline bool given(float v) { return v == v; }
+
 struct Matrix33 {  // tiny stand-in where no Eigen is around: anything with (i,j) works
   double m[9];
   double operator()(int i, int j) const { return m[3 * i + j]; }
@@ -97,11 +130,32 @@ class Fleet {
  public:
   // quadcopterType / ids are forwarded to logicType::Initialise exactly as
   // Quadcopter_T.cpp:82 does; `precision` AFE_F32 (production) or AFE_F64.
+  // battVoltage: what every logic is handed as its battery measurement (Quadcopter_T.cpp:72, 163) -- one value for the
+  // whole fleet, or (second form) one per type-table entry: vehicle i is handed battVoltagePerType[typeIndex[i]]
+  // (entry 0 without a typeIndex); the vector must have typeTable.size() entries.
   Fleet(BaseTimer *const masterTimer, int64_t nVehicles, const std::vector<afe_vehicle_params> &typeTable,
         const std::vector<uint8_t> &typeIndex, double onboardLogicPeriod, int precision = AFE_F32,
         int device = -1, float battVoltage = 0.0f)
       : _master(masterTimer), _integrationTimer(masterTimer), _n(nVehicles), _period(onboardLogicPeriod),
-        _battVoltage(battVoltage), _battCurrent(-1.0f) {  // Quadcopter_T.cpp:72-73
+        _battVoltage((size_t)(nVehicles > 0 ? nVehicles : 0), battVoltage), _battCurrent(-1.0f) {  // Quadcopter_T.cpp:72-73
+    init(masterTimer, nVehicles, typeTable, typeIndex, onboardLogicPeriod, precision, device);
+  }
+  Fleet(BaseTimer *const masterTimer, int64_t nVehicles, const std::vector<afe_vehicle_params> &typeTable,
+        const std::vector<uint8_t> &typeIndex, double onboardLogicPeriod, int precision, int device,
+        const std::vector<float> &battVoltagePerType)
+      : _master(masterTimer), _integrationTimer(masterTimer), _n(nVehicles), _period(onboardLogicPeriod),
+        _battVoltage((size_t)(nVehicles > 0 ? nVehicles : 0), 0.0f), _battCurrent(-1.0f) {
+    if (battVoltagePerType.size() != typeTable.size()) check(0, AFE_ERR_INVALID_ARG, "Fleet: one battery voltage per type-table entry");
+    else
+      for (size_t i = 0; i < _battVoltage.size(); i++) {
+        const size_t t = i < typeIndex.size() ? typeIndex[i] : 0;
+        if (t < battVoltagePerType.size()) _battVoltage[i] = battVoltagePerType[t];   // a bad index is afe_set_vehicle_types' to refuse
+      }
+    init(masterTimer, nVehicles, typeTable, typeIndex, onboardLogicPeriod, precision, device);
+  }
+ private:
+  void init(BaseTimer *const masterTimer, int64_t nVehicles, const std::vector<afe_vehicle_params> &typeTable,
+            const std::vector<uint8_t> &typeIndex, double onboardLogicPeriod, int precision, int device) {
     // the onboard logic runs on the host at every tick (Run() below): up to a few thousand vehicles the state arena
     // lives in host-visible memory, so that a Run() and the accessors after it cost bus latency, not transfer calls
     if (nVehicles <= 16384) check(0, afe_create_host_visible(&_e, nVehicles, precision, device, 0), "afe_create_host_visible");
@@ -115,6 +169,8 @@ class Fleet {
     _gyro.assign((size_t)(3 * nVehicles), 0.0f);
     _acc.assign((size_t)(3 * nVehicles), 0.0f);
   }
+
+ public:
   ~Fleet() { if (_e) afe_destroy(_e); }
   Fleet(const Fleet &) = delete;
   Fleet &operator=(const Fleet &) = delete;
@@ -139,7 +195,7 @@ class Fleet {
     const float TEMP_MEAS = 25;                         // :182
     for (int64_t i = 0; i < _n; i++) {                  // :163-189, same order
       logicType &L = _logic[(size_t)i];
-      L.SetBatteryMeasurement(_battVoltage, _battCurrent);
+      L.SetBatteryMeasurement(_battVoltage[(size_t)i], _battCurrent);
       L.SetIMUMeasurementRateGyro(_gyro[i], _gyro[_n + i], _gyro[2 * _n + i]);
       L.SetIMUMeasurementAccelerometer(_acc[i], _acc[_n + i], _acc[2 * _n + i]);
       L.SetIMUMeasurementTemperature(TEMP_MEAS);
@@ -181,7 +237,8 @@ class Fleet {
   Timer _integrationTimer;
   int64_t _n;
   double _period;
-  float _battVoltage, _battCurrent;
+  std::vector<float> _battVoltage;   // per vehicle
+  float _battCurrent;
   std::vector<logicType> _logic;
   std::vector<float> _cmd, _gyro, _acc;
 };
@@ -194,23 +251,28 @@ class Quadcopter_T : public Simulation::SimulationObject6DOF {
   // Same argument list as Quadcopter_T.hpp:24-32.  inertiaMatrix: anything with
   // operator()(i,j) (Eigen::Matrix<double,3,3> in the agri-fly tree).
   // quadcopterType is passed through to logicType::Initialise as an int-like
-  // value; lowBatteryThreshold / IMU mount angles come with the type in the
-  // reference (Quadcopter_T.cpp:71-77) and are explicit optional arguments here.
+  // value, and -- as in the reference (Quadcopter_T.cpp:71-77) -- the low-battery
+  // threshold and the IMU mount angles are derived from it (DeriveFromType above),
+  // so the reference's own fifteen-argument call hands the logic 1.2 x the type's
+  // threshold.  Each trailing argument, when given, overrides the derived value
+  // (an explicit 0 is an explicit 0; "not given" is FromType(), a NaN).
   template <class Matrix33T, class QuadcopterTypeT>
   Quadcopter_T(BaseTimer *const masterTimer, double mass, const Matrix33T &inertiaMatrix, double armLength,
                Vec3d centreOfMassError, double motorMinSpeed, double motorMaxSpeed,
                double propThrustFromSpeedSqr, double propTorqueFromSpeedSqr, double motorTimeConst,
                double motorInertia, Vec3d linDragCoeffB, uint8_t id, QuadcopterTypeT quadcopterType,
-               double onboardLogicPeriod, int precision = AFE_F32, float lowBatteryThreshold = 0.0f,
-               float imuYaw = 0, float imuPitch = 0, float imuRoll = 0)
+               double onboardLogicPeriod, int precision = AFE_F32, float lowBatteryThreshold = FromType(),
+               float imuYaw = FromType(), float imuPitch = FromType(), float imuRoll = FromType())
       : Simulation::SimulationObject6DOF(masterTimer),
+        _derived(resolve(quadcopterType, lowBatteryThreshold, imuYaw, imuPitch, imuRoll)),
         _fleet(masterTimer, 1,
                std::vector<afe_vehicle_params>(1, MakeParams(mass, inertiaMatrix, armLength, centreOfMassError,
                                                              motorMinSpeed, motorMaxSpeed, propThrustFromSpeedSqr,
                                                              propTorqueFromSpeedSqr, motorTimeConst, motorInertia,
-                                                             linDragCoeffB, imuYaw, imuPitch, imuRoll)),
+                                                             linDragCoeffB, _derived.imuYaw, _derived.imuPitch,
+                                                             _derived.imuRoll)),
                std::vector<uint8_t>(), onboardLogicPeriod, precision, -1,
-               1.2f * lowBatteryThreshold),  // Quadcopter_T.cpp:72
+               BatteryVoltage(_derived.lowBatteryThreshold)),  // Quadcopter_T.cpp:72
         _kThrust(propThrustFromSpeedSqr) {
     _radio.reset(new Simulation::UWBRadio(masterTimer, id));   // Quadcopter_T.cpp:68
     _fleet.logic(0).Initialise(quadcopterType, id);              // Quadcopter_T.cpp:82
@@ -289,6 +351,18 @@ class Quadcopter_T : public Simulation::SimulationObject6DOF {
     remember();
   }
 
+  template <class QuadcopterTypeT>
+  static TypeDerived resolve(QuadcopterTypeT quadcopterType, float lowBatteryThreshold, float imuYaw, float imuPitch,
+                             float imuRoll) {
+    TypeDerived d = DeriveFromType(quadcopterType);
+    if (given(lowBatteryThreshold)) d.lowBatteryThreshold = lowBatteryThreshold;
+    if (given(imuYaw)) d.imuYaw = imuYaw;
+    if (given(imuPitch)) d.imuPitch = imuPitch;
+    if (given(imuRoll)) d.imuRoll = imuRoll;
+    return d;
+  }
+
+  TypeDerived _derived;      // before _fleet: the fleet's parameters are made from it
   Fleet<logicType> _fleet;
   double _kThrust;
   double _sp[3], _sv[3], _sq[4], _sw[3];   // the state as of the last read-back

@@ -107,6 +107,12 @@ typedef struct afe_vehicle_params {
  * Pure host functions: usable without a GPU. */
 int afe_params_from_type(int quadcopter_type, afe_vehicle_params *out);
 int afe_type_from_id(unsigned vehicle_id);
+/* QuadcopterConstants(type).lowBatteryThreshold [V] for every type 0..5, the refused ones included -- perCellLowVoltage
+ * 3 V (QuadcopterConstants.hpp:50-51) times the cell count: 0 INVALID (:51), 1 CF_STANDARD 3 V (:83),
+ * 2 CF_BIGMOTORSPROPS 3 V (:117), 3 CF_FEEDTHROUGH 3 V (:150), 4 CF_LARGEQUAD 9 V (:180), 5 CF_MINIQUAD 6 V (:220).  The
+ * reference's vehicle hands its logic 1.2 x this as the battery measurement at every tick (Quadcopter_T.cpp:72, 163).
+ * NULL output or a type outside 0..5: AFE_ERR_INVALID_ARG. */
+int afe_low_battery_threshold_from_type(int quadcopter_type, float *volts);
 
 /* ---- lifetime -----------------------------------------------------------
  * Replaces `new Simulation::Quadcopter(...)` x n_vehicles (main.cpp:211-218;

@@ -11,6 +11,7 @@
  * Citations are file:line under /root/reference.
  */
 #include "agrifly_oracle.h"
+#include "agrifly_oracle_logic.h"
 
 #include <math.h>
 #include <string.h>
@@ -146,6 +147,13 @@ static void rotf_matrix(const float v[4], float R[9]) {
   R[6] = 2 * v[1] * v[3] - 2 * v[0] * v[2];
   R[7] = 2 * v[2] * v[3] + 2 * v[0] * v[1];
   R[8] = r0 - r1 - r2 + r3;
+}
+
+void ora_logic_set_imu_mount(ora_logic_params *p, float imu_yaw, float imu_pitch, float imu_roll) {
+  /* QuadcopterLogic.cpp:113-117: _R = Rotationf::FromEulerYPR(yaw, pitch, roll).GetRotationMatrix() */
+  float q[4];
+  rotf_from_euler_ypr(imu_yaw, imu_pitch, imu_roll, q);
+  rotf_matrix(q, p->R);
 }
 
 /* ------------------------------------------------------------------------ */

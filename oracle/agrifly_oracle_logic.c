@@ -109,7 +109,11 @@ void ora_logic_set_rates_cmd(ora_logic_state *s, float thrust_norm, const float 
   s->des_ang_vel[0] = w[0]; s->des_ang_vel[1] = w[1]; s->des_ang_vel[2] = w[2];
 }
 
+static ora_logic_branches *g_tally = 0;
+void ora_logic_count_branches(ora_logic_branches *tally) { g_tally = tally; }
+
 void ora_logic_tick(const ora_logic_params *p, ora_logic_state *s, const float gyro[3]) {
+  if (g_tally) g_tally->ticks++;
   /* SetIMUMeasurementRateGyro, QuadcopterLogic.hpp:40-45 (bias = 0, :145) */
   float raw[3];
   for (int i = 0; i < 3; i++) {
@@ -124,12 +128,14 @@ void ora_logic_tick(const ora_logic_params *p, ora_logic_state *s, const float g
    * the first call only initialises; afterwards _angVel = measGyro (:115) */
   if (!s->imu_initialized) {
     s->imu_initialized = 1;
+    if (g_tally) g_tally->first_imu++;
   } else {
     s->ang_vel_est[0] = filt[0]; s->ang_vel_est[1] = filt[1]; s->ang_vel_est[2] = filt[2];
   }
 
   if (!s->have_rates_cmd) { /* FS_IDLE: QuadcopterLogic.cpp:213-217 */
     for (int i = 0; i < 4; i++) { s->motor_speed_cmd[i] = 0; s->motor_force_cmd[i] = 0; }
+    if (g_tally) g_tally->idle++;
     return;
   }
 
@@ -150,18 +156,20 @@ void ora_logic_tick(const ora_logic_params *p, ora_logic_state *s, const float g
   /* QuadcopterMixer::GetMotorForces, QuadcopterMixer.hpp:63-86 */
   const float totF = s->thrust_norm * p->mass;
   const float desF = totF > p->max_cmd_total_thrust ? p->max_cmd_total_thrust : totF;
+  if (g_tally && totF > p->max_cmd_total_thrust) g_tally->cap++;
   float *F = s->motor_force_cmd;
   F[0] = (-t[0] / p->d - t[1] / p->d - t[2] / p->kt + desF) / 4.0f;
   F[1] = (-t[0] / p->d + t[1] / p->d + t[2] / p->kt + desF) / 4.0f;
   F[2] = (+t[0] / p->d + t[1] / p->d - t[2] / p->kt + desF) / 4.0f;
   F[3] = (+t[0] / p->d - t[1] / p->d + t[2] / p->kt + desF) / 4.0f;
   for (int i = 0; i < 4; i++) {
+    if (g_tally) { g_tally->lower += F[i] < p->min_thrust; g_tally->upper += !(F[i] < p->min_thrust) && F[i] > p->max_thrust; }
     if (F[i] < p->min_thrust) F[i] = p->min_thrust;
     else if (F[i] > p->max_thrust) F[i] = p->max_thrust;
   }
   /* PropellerSpeedsFromThrust, QuadcopterMixer.hpp:88-99 (correction factors 1) */
   for (int i = 0; i < 4; i++) {
-    if (F[i] <= 0) { s->motor_speed_cmd[i] = 0; continue; }
+    if (F[i] <= 0) { s->motor_speed_cmd[i] = 0; if (g_tally) g_tally->f_le0++; continue; }
     s->motor_speed_cmd[i] = sqrtf(F[i] / (1.0f * p->kf));
   }
 }

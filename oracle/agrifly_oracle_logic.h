@@ -13,7 +13,9 @@
  * LowPassFilterSecondOrder.hpp and QuadcopterConstants.hpp (they use Eigen for
  * storage only) composed inside the reference's Quadcopter_T::Run (oracle/_ref/
  * rigid_body_probe, tests/golden/rigid_body_closed_loop.npz: ClosedLoopBatch
- * equals the recording bit for bit, tests/test_rigid_body_reference.py).  The
+ * equals the recording bit for bit, tests/test_rigid_body_reference.py); the
+ * type constants also directly, member by member (oracle/_ref/constants_probe,
+ * tests/golden/vehicle_constants.json, tests/test_vehicle_constants.py).  The
  * call sequence between them -- the first IMU call initialises only, thrust_norm
  * * mass, idle until a rates command arrives -- stays **parity unpinned**:
  * QuadcopterLogic.cpp and KalmanFilter6DOF.cpp do Eigen arithmetic and are not
@@ -59,6 +61,22 @@ void ora_logic_init(const ora_logic_params *p, ora_logic_state *s);
 void ora_logic_set_rates_cmd(ora_logic_state *s, float thrust_norm, const float des_ang_vel[3]);
 /* one tick: SetIMUMeasurementRateGyro(gyro) ... Run() in rates mode */
 void ora_logic_tick(const ora_logic_params *p, ora_logic_state *s, const float gyro[3]);
+/* p->R = Rotationf::FromEulerYPR(yaw, pitch, roll).GetRotationMatrix(), QuadcopterLogic.cpp:113-117 (defined in
+ * agrifly_oracle.c beside the float rotation helpers that ora_params_init uses for the inverse mount) */
+void ora_logic_set_imu_mount(ora_logic_params *p, float imu_yaw, float imu_pitch, float imu_roll);
+
+/* Which branches ora_logic_tick took (a coverage tally for tests; changes no result).  While a tally is registered
+ * every tick adds to it; NULL (the default) switches the counting off.  One tally at a time, not thread-safe. */
+typedef struct ora_logic_branches {
+  unsigned long long ticks;
+  unsigned long long idle;        /* no rates command yet: commands 0 */
+  unsigned long long first_imu;   /* the call that only initialises the estimator */
+  unsigned long long cap;         /* thrust_norm * mass above the total-thrust cap */
+  unsigned long long lower;       /* per motor: F below min_thrust */
+  unsigned long long upper;       /* per motor: F above max_thrust */
+  unsigned long long f_le0;       /* per motor: F <= 0 after the clamps, speed command 0 */
+} ora_logic_branches;
+void ora_logic_count_branches(ora_logic_branches *tally);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,14 @@
 // the vehicle of Simulator/Rappids_Simulator/main.cpp:146-218 constructed with the SAME argument list, but as
 // agrifly::Quadcopter_T<Onboard::QuadcopterLogic>, held the way the loops hold it (main.cpp:211;
 // AIFS_ROS/hiperlab_rostools/src/Simulator/main.cpp:83) and driven through every member of the upper seam the two mains
-// call.  It is never RUN by the CPU suite (it needs an MI355X); it exists so that a signature drift between the façade
-// and the reference's SimulationObject6DOF / Quadcopter_T / logicType concept fails a build.  Pins nothing.
+// call.  That flight is never RUN by the CPU suite (it needs an MI355X); it exists so that a signature drift between the
+// façade and the reference's SimulationObject6DOF / Quadcopter_T / logicType concept fails a build.
+// One path IS run, by the recipe at build time: `dropin derive` makes no engine and checks what the façade derives from a
+// quadcopterType where the reference's constructor reads Onboard::QuadcopterConstants (Quadcopter_T.cpp:70-80) -- the
+// battery voltage handed to the logic, 1.2f * lowBatteryThreshold, and the IMU mount angles -- for every type of the
+// tree's enum, against the tree's own header and against the engine library's own table.
+#include <cstdio>
+#include <cstring>
 #include <memory>
 
 #include "Common/Time/ManualTimer.hpp"
@@ -21,7 +27,32 @@ namespace Simulation {
 typedef agrifly::Quadcopter_T<Onboard::QuadcopterLogic> Quadcopter;
 }
 
-int main() {
+static uint32_t bits(float v) { uint32_t b; std::memcpy(&b, &v, 4); return b; }
+
+// no engine call: agrifly::DeriveFromType / BatteryVoltage and the library's pure-host table only
+static int check_derived() {
+  int bad = 0;
+  for (int t = 0; t < (int)Onboard::QuadcopterConstants::QC_TYPE_COUNT; t++) {
+    const Onboard::QuadcopterConstants::QuadcopterType type = (Onboard::QuadcopterConstants::QuadcopterType)t;
+    Onboard::QuadcopterConstants consts(type);
+    const agrifly::TypeDerived d = agrifly::DeriveFromType(type);
+    const float volts = agrifly::BatteryVoltage(d.lowBatteryThreshold), want = 1.2f * consts.lowBatteryThreshold;
+    float table = -1.0f;
+    const int rc = afe_low_battery_threshold_from_type(t, &table);
+    const bool ok = bits(volts) == bits(want) && bits(d.imuYaw) == bits(consts.IMU_yaw) &&
+                    bits(d.imuPitch) == bits(consts.IMU_pitch) && bits(d.imuRoll) == bits(consts.IMU_roll) &&
+                    rc == AFE_OK && bits(table) == bits(consts.lowBatteryThreshold);
+    std::printf("type %d: battery %.9g V (want %.9g), mount %.9g %.9g %.9g (want %.9g %.9g %.9g), library threshold %.9g V "
+                "(rc %d, want %.9g): %s\n", t, volts, want, d.imuYaw, d.imuPitch, d.imuRoll, consts.IMU_yaw, consts.IMU_pitch,
+                consts.IMU_roll, table, rc, consts.lowBatteryThreshold, ok ? "ok" : "MISMATCH");
+    if (!ok) bad++;
+  }
+  std::printf("%s\n", bad ? "derive FAILED" : "derive ok");
+  return bad ? 1 : 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "derive")) return check_derived();
   ManualTimer simTimer;                                                     // main.cpp:143
   // main.cpp:146-177, verbatim in meaning
   uint8_t vehicleId = 1;

@@ -59,3 +59,19 @@ def test_the_reference_branch_uses_the_trees_own_base_class():
     compiled -fsyntax-only -Werror by the recipe; the stamp exists only if that compile succeeded)"""
     assert os.path.exists(BASE_OK), _read(os.path.join(OUT, "dropin_base.log"))[-4000:]
     assert os.path.getmtime(BASE_OK) >= os.path.getmtime(os.path.join(ROOT, "tests", "cpp", "dropin_base_check.cpp"))
+
+
+@pytest.mark.skipif(not os.path.exists(EXE + ".log"), reason="build() compiled no drop-in check: the agri-fly tree was absent (oracle/Makefile REF)")
+def test_what_the_facade_derives_from_the_type_is_the_reference_constructors():
+    """The one path of oracle/_ref/dropin that IS run (by the recipe, at build time; it makes no engine): for every type of
+    the tree's enum, agrifly::DeriveFromType / BatteryVoltage -- what the façade's constructor uses where the caller gives
+    the reference's own fifteen arguments -- equal, bit for bit, 1.2f * QuadcopterConstants(type).lowBatteryThreshold and
+    the header's IMU_yaw / _pitch / _roll (Quadcopter_T.cpp:70-80), and the engine library's own table
+    (afe_low_battery_threshold_from_type) equals the header's threshold.  The stamp exists only if every line agreed."""
+    log = _read(os.path.join(OUT, "dropin_derive.log"))
+    assert os.path.exists(os.path.join(OUT, "dropin_derive.ok")), log[-3000:]
+    lines = log.splitlines()
+    assert lines[-1] == "derive ok" and len(lines) == 7 and all(l.endswith(": ok") for l in lines[:6]), log[-3000:]
+    assert [l.split(":")[0] for l in lines[:6]] == ["type %d" % t for t in range(6)]
+    # not a stale stamp: made from the program as it is now
+    assert os.path.getmtime(os.path.join(OUT, "dropin_derive.ok")) >= os.path.getmtime(EXE)
