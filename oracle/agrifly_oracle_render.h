@@ -21,7 +21,18 @@
  *     vehicle position (main.cpp:123-125,520-523).
  * The geometry is a brute-force ray / triangle test over every triangle
  * (Moeller-Trumbore, two-sided), the independent check for the engine's BVH
- * traversal.
+ * traversal.  Triangles are CLOSED sets and the test is watertight across
+ * shared edges: it decides on the barycentric numerators with the tolerance
+ * eps = 2^-48 |d|_1 E (|tv|_1 + E), E = max(|e1|_1, |e2|_1) -- 32 units of
+ * roundoff on the bound of the sum of absolute products, where rounding moves
+ * a numerator by at most 18 -- so a ray that lies on an edge or a vertex is
+ * accepted by a triangle it lies in, whichever way the products round.  A
+ * triangle whose |det| is not above eps max(1, 2^15 E) is edge-on as far as
+ * fp64 can tell and hits nothing (a cutoff relative to the operands), as does
+ * a zero-area triangle.  The engine performs the same operations in the same
+ * order (images agree bit for bit); whether they match the GEOMETRY is judged
+ * by tests/render_judge.py in exact arithmetic, for the checker on a CPU and
+ * for the kernel on the GPU.
  */
 #ifndef AGRIFLY_ORACLE_RENDER_H
 #define AGRIFLY_ORACLE_RENDER_H

@@ -93,6 +93,25 @@ def test_degenerate_meshes(ora):
         afa.Scene(np.full((1, 9), np.nan, np.float32))
 
 
+def test_centred_camera_in_the_closed_box(ora):
+    """test_degenerate_meshes steps its camera aside so that no ray runs exactly into a corner of the box.  Here it does not:
+    from (0, 0, 1), facing each of the four walls, pixel (0, 25) looks straight into a corner and others along edges and the
+    faces' diagonals.  Triangles are closed and watertight across shared edges, so every pixel hits, the image is the
+    checker's, and it passes the exact-geometry judge (tests/render_judge.py)."""
+    from tests import render_scenes as rs
+    from tests.render_judge import assert_passes
+    views = [v for v in rs.box_views() if v.name.startswith("box 40x30")]
+    assert len(views) == 4
+    for view in views:
+        scene = afa.Scene(view.tris)
+        for plain in (False, True):
+            scene.set_walk(plain)
+            got, _ = _check(ora, scene, view.cam.afa(afa), view.tris, view.pos.reshape(3, 1), view.att.reshape(4, 1), view.mount)
+            assert got.max() < 255
+            assert_passes(rs.judged(view), got[0], view.name)
+        scene.close()
+
+
 @pytest.mark.parametrize("precision", [AFE_F64, AFE_F32])
 def test_poses_from_engine_state(ora, precision):
     tris = scen.orchard_mesh(rows=4, cols=4, seed=21)
