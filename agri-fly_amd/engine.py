@@ -61,6 +61,8 @@ ABI_FUNCTIONS = [
     "afe_image_truth_sample_times", "afe_image_truth_paths", "afe_image_truth_paths_stats", "afe_image_truth_plans",
     "afe_image_truth_candidates", "afe_device_upload",
     "afe_low_battery_threshold_from_type",
+    "afe_raycast", "afe_raycast_stats", "afe_line_of_sight",
+    "afe_range_sensor_create", "afe_range_sensor_update", "afe_range_sensor_info", "afe_range_sensor_destroy",
 ]
 
 
@@ -414,6 +416,13 @@ def library():
         "afe_image_truth_plans": [ci, C.POINTER(PlannerConfig), i64, vp, i64, ci, vp, vp, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)],
         "afe_image_truth_candidates": [ci, C.POINTER(PlannerConfig), i64, vp, i64, ci, vp, vp, vp, vp, ci, vp, ci, vp, C.c_double, vp, vp, vp, vp,
                                        C.POINTER(C.c_float)],
+        "afe_raycast": [vp, i64, vp, vp, vp, vp, vp, C.POINTER(C.c_float)],
+        "afe_raycast_stats": [vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)],
+        "afe_line_of_sight": [vp, i64, vp, vp, vp, C.POINTER(C.c_float)],
+        "afe_range_sensor_create": [eng, vp, vp, vp, ci, C.POINTER(vp)],
+        "afe_range_sensor_update": [vp, i64, i64, vp, vp, ci, C.POINTER(C.c_float)],
+        "afe_range_sensor_info": [vp, C.POINTER(ci), C.POINTER(i64)],
+        "afe_range_sensor_destroy": [vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -822,6 +831,44 @@ class ClearanceMap:
         _status(library().afe_clearance_segments_stats(self._h, n, a.ctypes.data, b.ctypes.data, float(max_dist), st.ctypes.data, C.byref(ms)))
         return dict(zip(("nodes", "tri_box_tests", "tri_fp64_evals", "segments"), (int(x) for x in st))), ms.value
 
+    def _ray_arrays(self, origin, dir, t_max):
+        n, o, d = self._segment_arrays(origin, dir)
+        tm = None if t_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n,)))
+        return n, o, d, tm
+
+    def raycast(self, origin, dir, t_max=None, want_ms=False):
+        """n rays ([3, n] origins and directions, neither normalised; t_max None, a scalar or [n]) -> (t [n], tri [n] int32):
+        the first triangle each ray hits and its ray parameter (metres for unit directions); no hit: (+inf, -1).
+        See the header, range beams.  want_ms: (t, tri, kernel_ms)."""
+        n, o, d, tm = self._ray_arrays(origin, dir, t_max)
+        t, tri = np.empty(n), np.empty(n, np.int32)
+        ms = C.c_float(0)
+        _status(library().afe_raycast(self._h, n, o.ctypes.data, d.ctypes.data, None if tm is None else tm.ctypes.data, t.ctypes.data,
+                                      tri.ctypes.data, C.byref(ms)))
+        return (t, tri, ms.value) if want_ms else (t, tri)
+
+    def raycast_stats(self, origin, dir, t_max=None, want_answers=False):
+        """traversal counters of such a batch (counting build), summed over the rays: dict + kernel_ms; want_answers: and
+        the counting build's own (t, tri)"""
+        n, o, d, tm = self._ray_arrays(origin, dir, t_max)
+        st = np.zeros(4, np.uint64)
+        t, tri = np.empty(n), np.empty(n, np.int32)
+        ms = C.c_float(0)
+        _status(library().afe_raycast_stats(self._h, n, o.ctypes.data, d.ctypes.data, None if tm is None else tm.ctypes.data,
+                                            t.ctypes.data if want_answers else None, tri.ctypes.data if want_answers else None,
+                                            st.ctypes.data, C.byref(ms)))
+        counts = dict(zip(("nodes", "tri_box_tests", "tri_fp64_tests", "rays"), (int(x) for x in st)))
+        return (counts, ms.value, t, tri) if want_answers else (counts, ms.value)
+
+    def line_of_sight(self, p0, p1, want_ms=False):
+        """n pairs ([3, n] each) -> blocked [n] uint8: 1 where a triangle lies between p0 and p1 (a hit with 0 < t <= 1 of
+        the ray p0 + t (p1 - p0)), else 0.  want_ms: (blocked, kernel_ms)."""
+        n, a, b = self._segment_arrays(p0, p1)
+        out = np.empty(n, np.uint8)
+        ms = C.c_float(0)
+        _status(library().afe_line_of_sight(self._h, n, a.ctypes.data, b.ctypes.data, out.ctypes.data, C.byref(ms)))
+        return (out, ms.value) if want_ms else out
+
     def query_engine(self, ensemble, max_dist, first=0, count=None, out=None):
         """The same for vehicles [first, first+count) from the engine's device state.  out: None to get
         (dist2, tri, closest, kernel_ms) on the host, or a (dist2, tri, closest) tuple of DeviceBuffers (closest may
@@ -1066,6 +1113,75 @@ class ContactMonitor:
     def close(self):
         if getattr(self, "_h", None):
             library().afe_contact_monitor_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# afe_range_beam: one beam of a range sensor (64 bytes)
+RANGE_BEAM_DTYPE = np.dtype([("off", np.float64, 3), ("dir", np.float64, 3), ("t_max", np.float64), ("frame", np.int32), ("reserved", np.int32)])
+RANGE_FRAME_SENSOR, RANGE_FRAME_WORLD = 0, 1
+
+
+def range_beam(dir, off=(0.0, 0.0, 0.0), t_max=np.inf, frame=RANGE_FRAME_SENSOR):
+    """One RANGE_BEAM_DTYPE record."""
+    b = np.zeros((), RANGE_BEAM_DTYPE)
+    b["off"], b["dir"], b["t_max"], b["frame"] = off, dir, t_max, frame
+    return b
+
+
+def crazyflie_range_beams(t_max=4.0):
+    """The six beams of a Crazyflie's multi-ranger and z-ranger decks: +x, -x, +y, -y, +z, -z of the sensor frame from its
+    origin, t_max metres each (the decks' VL53L1x reaches about 4 m) -> RANGE_BEAM_DTYPE [6]."""
+    dirs = ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))
+    return np.array([range_beam(np.array(d, np.float64), t_max=t_max) for d in dirs], RANGE_BEAM_DTYPE)
+
+
+class RangeSensor:
+    """afe_range_sensor: beams mounted on every vehicle of an ensemble, answered from the engine's device state against a
+    ClearanceMap (see the header, range beams).  beams: RANGE_BEAM_DTYPE [1 .. 32]; mount: quaternion of the sensor frame
+    in the body frame (None: identity).  Borrows the ensemble and the map: close it before either of them."""
+
+    def __init__(self, ensemble, cmap, beams, mount=None):
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = (ensemble, cmap)
+        b = np.ascontiguousarray(beams, dtype=RANGE_BEAM_DTYPE).reshape(-1)
+        m = None if mount is None else np.ascontiguousarray(mount, dtype=np.float64)
+        assert m is None or m.shape == (4,)
+        self.n_beams = b.size
+        _status(library().afe_range_sensor_create(ensemble.handle, cmap.handle, None if m is None else m.ctypes.data, b.ctypes.data,
+                                                  b.size, C.byref(self._h)))
+
+    def update(self, first=0, count=None, out=None, want_ms=True):
+        """Vehicles [first, first+count) now.  out: None to get (t [n_beams, count], tri [n_beams, count] int32, kernel_ms) on
+        the host, or a (t, tri) tuple of DeviceBuffers (tri may be None) to keep the readings in HBM (returns kernel_ms, or
+        None without waiting if want_ms is false)."""
+        count = self.n - first if count is None else count
+        ms = C.c_float(0)
+        ms_ptr = C.byref(ms) if want_ms else None
+        if out is None:
+            t, tri = np.empty((self.n_beams, max(count, 0))), np.empty((self.n_beams, max(count, 0)), np.int32)
+            _status(library().afe_range_sensor_update(self._h, int(first), int(count), t.ctypes.data, tri.ctypes.data, 0, ms_ptr))
+            return t, tri, ms.value
+        b_t, b_tri = out
+        assert b_t.nbytes >= self.n_beams * count * 8 and (b_tri is None or b_tri.nbytes >= self.n_beams * count * 4)
+        _status(library().afe_range_sensor_update(self._h, int(first), int(count), b_t.ptr, None if b_tri is None else b_tri.ptr, 1, ms_ptr))
+        return ms.value if want_ms else None
+
+    def info(self):
+        nb, nv = C.c_int(), C.c_int64()
+        _status(library().afe_range_sensor_info(self._h, C.byref(nb), C.byref(nv)))
+        return {"n_beams": nb.value, "n_vehicles": nv.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_range_sensor_destroy(self._h)
             self._h = C.c_void_p()
             self._keep = None
 

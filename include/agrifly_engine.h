@@ -717,6 +717,64 @@ int afe_contact_monitor_destroy(afe_contact_monitor *c);   /* NULL is AFE_ERR_IN
 int afe_contact_monitor_create_swept(afe_engine *e, afe_clearance_map *m, double contact_radius, double search_radius,
                                      afe_contact_monitor **out);
 
+/* ---- range beams: what one arbitrary ray hits first, and how far away -------------------------------------------
+ * On the clearance map's own tree.  csrc/afe_raycast.hip states the definition, tests/raycast_checker.py restates it
+ * in numpy; the two agree bit for bit and no output bit depends on the hierarchy.  IEEE double, contraction off.
+ *   One ray (origin o, direction d, neither normalised) against one triangle: the depth camera's closed, watertight
+ *   rule (the one behind afe_render_depth and its CPU checker, operation for operation): v0, e1 = v1 - v0, e2 = v2 - v0 in
+ *   double; p = d x e2; det = e1.p; tv = o - v0; en = max(|e1|_1, |e2|_1); dn = |d|_1;
+ *   eps = (dn * (2^-48 * en)) * (|tv|_1 + en); miss unless |det| > eps * max(1, 32768 en); s = sign(det);
+ *   nu = (tv.p) s, miss if nu < -eps; q = tv x e1; nv = (d.q) s, miss if nv < -eps; miss if (|det| - nu) - nv < -eps;
+ *   t = (e2.q) * (1 / det); a hit iff t > 0.  The map's degenerate flag is not consulted.
+ *   WINNER: only hits with t <= t_max count (+inf: no limit); the smallest t wins, among bitwise-equal t the lowest
+ *   index in the order given to afe_clearance_map_create.  No hit: (+inf, -1).  A ray with a non-finite component in
+ *   o or d: the same, without a walk.  d = 0 hits nothing.  An origin ON a triangle does not hit it (t > 0).
+ * t is the ray PARAMETER: metres when |d|_2 = 1.
+ * afe_raycast: n rays, origin and dir planar [3][n] doubles, t_max [n] or NULL (no limit); t_out [n], tri_out [n].
+ * Refused: NULLs, n < 0 (AFE_ERR_INVALID_ARG); a t_max entry that is NaN or negative, n > 2^40 (AFE_ERR_OUT_OF_RANGE).
+ * n == 0 is AFE_OK with no launch. */
+int afe_raycast(afe_clearance_map *m, int64_t n, const double *origin, const double *dir, const double *t_max,
+                double *t_out, int32_t *tri_out, float *kernel_ms);
+/* The counting build for such a batch, a second compilation of the same walk: stats[0] tree nodes visited, [1] triangle
+ * box tests, [2] double-precision ray/triangle tests, [3] rays.  t_out and tri_out may be NULL; given, they receive the
+ * answers, which are afe_raycast's.  n <= 0 is AFE_ERR_INVALID_ARG. */
+int afe_raycast_stats(afe_clearance_map *m, int64_t n, const double *origin, const double *dir, const double *t_max,
+                      double *t_out, int32_t *tri_out, uint64_t stats[4], float *kernel_ms);
+/* Line of sight from p0 to p1 (planar [3][n] doubles): d = p1 - p0 per axis; blocked[i] = 1 iff the first-hit query
+ * with o = p0 and t_max = 1 has a hit, else 0 (a triangle touched at t = 1 exactly blocks; p0 == p1 never does; a
+ * non-finite end gives 0).  Served by the first-hit kernel or by one that stops at the first hit with t <= 1: the
+ * answer is the same.  n == 0 is AFE_OK. */
+int afe_line_of_sight(afe_clearance_map *m, int64_t n, const double *p0, const double *p1, uint8_t *blocked,
+                      float *kernel_ms);
+
+/* A RANGE SENSOR on an engine: a mount quaternion (sensor frame in the body frame, like the camera's; NULL: identity)
+ * and 1 .. 32 beams.  The vehicle's origin o_v and matrix R are those of the camera pose (att * mount; anchors added in
+ * double; fp32 or fp64 slabs; R is not normalised).  Per beam:
+ *   frame 0 (sensor frame):  origin w.x = o_v.x + ((R0*off.x + R1*off.y) + R2*off.z), rows 1 and 2 for y and z;
+ *                            direction d.x = (R0*dir.x + R1*dir.y) + R2*dir.z, likewise
+ *   frame 1 (world frame, a levelled beam such as height above canopy):  w = o_v + off per axis, d = dir
+ * then the first-hit query with the beam's t_max (+inf: no limit).  t is in metres when |dir|_2 = 1 and the
+ * quaternions are unit.  A vehicle with a non-finite position or attitude reads (+inf, -1) on every beam. */
+typedef struct afe_range_beam {          /* 64 bytes; the layout is ABI */
+  double  off[3], dir[3], t_max;
+  int32_t frame, reserved;
+} afe_range_beam;
+typedef struct afe_range_sensor afe_range_sensor;
+/* Refused: NULLs, non-finite mount, off or dir (AFE_ERR_INVALID_ARG); n_beams outside 1 .. 32, a t_max that is NaN or
+ * negative, a frame other than 0 or 1 (AFE_ERR_OUT_OF_RANGE); then the engine's gate; then a map on another device than
+ * the engine (AFE_ERR_INVALID_ARG).  The sensor BORROWS engine and map: destroy it before either of them. */
+int afe_range_sensor_create(afe_engine *e, afe_clearance_map *m, const double mount[4], const afe_range_beam *beams,
+                            int n_beams, afe_range_sensor **out);
+/* Vehicles [first, first + count) at the engine's current state: t_out [n_beams][count] doubles, tri_out
+ * [n_beams][count] int32 (may be NULL); device pointers if out_is_device, else host arrays.  Ordered on the engine's
+ * stream; a resident step grid ends first.  With device outputs and kernel_ms == NULL the call does not wait.
+ * count == 0 with a valid range returns AFE_OK without touching the engine; a range beyond the engine is
+ * AFE_ERR_OUT_OF_RANGE. */
+int afe_range_sensor_update(afe_range_sensor *s, int64_t first, int64_t count, void *t_out, void *tri_out,
+                            int out_is_device, float *kernel_ms);
+int afe_range_sensor_info(const afe_range_sensor *s, int *n_beams, int64_t *n_vehicles);
+int afe_range_sensor_destroy(afe_range_sensor *s);   /* NULL is AFE_ERR_INVALID_ARG */
+
 /* ---- ensemble statistics ---------------------------------------------------
  * What a Monte-Carlo sweep ends with: the distribution of the ensemble's state
  * per parameter bin, now and over the flight, without downloading the state.
