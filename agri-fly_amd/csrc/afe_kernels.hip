@@ -63,16 +63,6 @@ __device__ __forceinline__ void mat_vec(const M *A, R x, R y, R z, R &ox, R &oy,
 }
 
 // ---------------------------------------------------------------------------
-#ifndef AFE_KERNARG_RELOAD
-#define AFE_KERNARG_RELOAD 1   // 0: the headline instantiation of the resident grid keeps its kernel arguments in registers across its loops like the others, kept for A/B timing
-#endif
-#ifndef AFE_EXACT_TRIMS
-#define AFE_EXACT_TRIMS 1      // 0: the accepted candidates evaluated with libstdc++'s operations one for one (2 c - 1 in two roundings, the canonical value clamped below 1), kept for A/B timing
-#endif
-#ifndef AFE_ACCEPT_LOOP
-#define AFE_ACCEPT_LOOP 2   // 1: the first form of the acceptance loop (selects on a slot number), kept for A/B timing
-#endif
-
 // IMU noise: std::minstd_rand0 + libstdc++ std::normal_distribution<double>
 // (reference Quadcopter_T.hpp:122-123; bits/random.tcc), always in double.
 __device__ __forceinline__ uint32_t minstd_next(uint32_t &s) {
@@ -111,10 +101,7 @@ __device__ __forceinline__ double canonical53(uint32_t &s) {
   // rounded quotient reaches 1.0 only for a high word of 2147483646 (any smaller one leaves it at most 1 - 4.6e-10) AND a
   // low word within 256 of the top, but the high word is 16807 times the low word mod 2^31 - 1, so a high word of 2147483646
   // (== -1) fixes the low one at 2^31 - 1 - 16807^-1 = 739806647 and the quotient at 1 - 3.05e-10.  Left out (a compare and two
-  // selects per call, 18 vector instructions per tick); AFE_EXACT_TRIMS=0 puts it back.  tests/test_gpu_noise_loop.py holds the argument.
-#if !AFE_EXACT_TRIMS
-  if (ret >= 1.0) ret = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
-#endif
+  // selects per call, 18 vector instructions per tick).  tests/test_gpu_noise_loop.py holds the argument.
   return ret;
 }
 
@@ -194,13 +181,8 @@ __device__ __forceinline__ void polar_candidate(uint32_t &s, double &x, double &
 #pragma clang fp contract(off)
   // 2 c - 1 as ONE fma: 2 c is exact (c < 1, a power-of-two factor), so the fma rounds the same real number that
   // libstdc++'s separately rounded product and difference do -- the same double, one fp64 instruction less per coordinate
-#if AFE_EXACT_TRIMS
   x = __builtin_fma(2.0, canonical53(s), -1.0);
   y = __builtin_fma(2.0, canonical53(s), -1.0);
-#else
-  x = 2.0 * canonical53(s) - 1.0;
-  y = 2.0 * canonical53(s) - 1.0;
-#endif
   r2 = x * x + y * y;
 }
 
@@ -220,8 +202,7 @@ __device__ __forceinline__ void polar_candidate(uint32_t &s, double &x, double &
 //     integer and fp32 only.
 __device__ __forceinline__ void three_accepted(uint32_t &s, uint32_t &st0, uint32_t &st1, uint32_t &st2) {
 #pragma clang fp contract(off)
-#if AFE_ACCEPT_LOOP == 2
-  // Second form (same decisions, same words).  Issue cost, not instruction count, is what the tick launch is
+  // Issue cost, not instruction count, is what the tick launch is
   // bound by, and on this chip a compare (it writes a scalar mask) costs 2.4x and a select 1.8x a plain integer
   // instruction (tools/valu_rate_probe.hip).  So: the two-sided range test is ONE unsigned compare on the float's
   // bit pattern (r2~ >= 0: bit patterns order like the values); "too close to call" is one more; and the three
@@ -238,9 +219,13 @@ __device__ __forceinline__ void three_accepted(uint32_t &s, uint32_t &st0, uint3
                  kTop = __builtin_bit_cast(uint32_t, 1.0f + 1e-5f);
   for (;;) {
     const uint32_t before = s;
+    // of the four words a candidate consumes the decision needs only the 2nd and the 4th (the high
+    // halves of the two uniforms), and the 4th is also the engine word afterwards: x_{n+2} = a^2 x_n and
+    // x_{n+4} = a^4 x_n (mod 2^31 - 1), two independent multiplications instead of four chained ones
     const uint32_t hx = minstd_mul(before, 282475249u);    // 16807^2
     const uint32_t hy = minstd_mul(before, 984943658u);    // 16807^4 mod (2^31 - 1)
     s = hy;
+    // c ~ (h - 1) / R: x~ = 2 c~ - 1, |x~ - x| < 4e-7; |r2~ - r2| < 2e-6
     const float kInvR = 1.0f / 2147483646.0f;
     const float xf = __builtin_fmaf((float)(hx - 1u), 2.0f * kInvR, -1.0f);
     const float yf = __builtin_fmaf((float)(hy - 1u), 2.0f * kInvR, -1.0f);
@@ -264,41 +249,6 @@ __device__ __forceinline__ void three_accepted(uint32_t &s, uint32_t &st0, uint3
     m3 |= m2 & am; m2 |= m1 & am; m1 |= am;
     if (__builtin_amdgcn_inverse_ballot_w64(m3)) break;
   }
-#else
-  st0 = s; st1 = s; st2 = s;   // engine word before the 1st / 2nd / 3rd accepted candidate
-  int got = 0;
-  while (got < 3) {
-    const uint32_t before = s;
-    // of the four words a candidate consumes the decision needs only the 2nd and the 4th (the high
-    // halves of the two uniforms), and the 4th is also the engine word afterwards: x_{n+2} = a^2 x_n and
-    // x_{n+4} = a^4 x_n (mod 2^31 - 1), two independent multiplications instead of four chained ones
-    const uint32_t hx = minstd_mul(before, 282475249u);    // 16807^2
-    const uint32_t hy = minstd_mul(before, 984943658u);    // 16807^4 mod (2^31 - 1)
-    s = hy;
-    // c ~ (h - 1) / R: x~ = 2 c~ - 1, |x~ - x| < 4e-7; |r2~ - r2| < 2e-6
-    const float kInvR = 1.0f / 2147483646.0f;
-    const float xf = __builtin_fmaf((float)(hx - 1u), 2.0f * kInvR, -1.0f);
-    const float yf = __builtin_fmaf((float)(hy - 1u), 2.0f * kInvR, -1.0f);
-    const float r2f = __builtin_fmaf(xf, xf, yf * yf);
-    bool accept = r2f < 1.0f - 1e-5f && r2f > 1e-5f;
-    const bool unsure = !accept && !(r2f > 1.0f + 1e-5f);   // too close to call in fp32
-    if (__ballot(unsure)) {   // wave-uniform on purpose: a real branch around the double-precision test, taken ~1e-3 of the time
-      if (unsure) {
-        uint32_t t = before;
-        asm volatile("" : "+v"(t));   // pins the double-precision test inside the branch (the compiler would otherwise run it speculatively every iteration)
-        double x, y, r2;
-        polar_candidate(t, x, y, r2);
-        accept = !(r2 > 1.0 || r2 == 0.0);
-      }
-    }
-    // straight-line bookkeeping (selects, no branches): slot `got` takes the word if accepted
-    const int slot = accept ? got : 3;
-    st0 = slot == 0 ? before : st0;
-    st1 = slot == 1 ? before : st1;
-    st2 = slot == 2 ? before : st2;
-    got += accept ? 1 : 0;
-  }
-#endif
 }
 
 // double precision throughout: the fp64 engine and the generator self-test (libstdc++'s values to 4e-15)
@@ -485,10 +435,6 @@ __device__ __forceinline__ void rotvec_to_quat(float rx, float ry, float rz,
     d3 = sc * rz;
   }
 }
-
-#ifndef AFE_LOGIC_LOADS_LATE
-#define AFE_LOGIC_LOADS_LATE 1
-#endif
 
 template <typename R> struct NormalOf { typedef double type; };
 template <> struct NormalOf<float> { typedef float type; };
@@ -729,8 +675,8 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
   } while (0)
   // The logic's own state (filter memory, commands: 18 registers) is wanted only at the tick.  A launch of several
   // sub-steps fetches it here with everything else; the one-step launch fetches it behind the rigid-body update
-  // (AFE_LOGIC_LOADS_LATE), where the draws and the dynamics no longer need the registers.
-  if (LOGIC && tick_mask && !(SINGLE && AFE_LOGIC_LOADS_LATE)) AFE_LOAD_LOGIC_STATE();
+  // (below), where the draws and the dynamics no longer need the registers.
+  if (LOGIC && tick_mask && !SINGLE) AFE_LOAD_LOGIC_STATE();
   float cmd_new[4] = {0, 0, 0, 0};
 
   const R dt = v.dt;
@@ -915,8 +861,8 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
     wx = nwx; wy = nwy; wz = nwz;
 
     // The one-step logic launch writes the rigid-body state back as soon as it is final instead of at the end:
-    // the registers are then free for the logic's own state (AFE_LOGIC_LOADS_LATE).
-    if (LOGIC && SINGLE && AFE_LOGIC_LOADS_LATE) {
+    // the registers are then free for the logic's own state.
+    if (LOGIC && SINGLE) {
       AFE_ST(R, pos, 0, off, px); AFE_ST(R, pos, 1, off, py); AFE_ST(R, pos, 2, off, pz);
       AFE_ST(R, vel, 0, off, vx); AFE_ST(R, vel, 1, off, vy); AFE_ST(R, vel, 2, off, vz);
       AFE_ST(R, att, 0, off, q0); AFE_ST(R, att, 1, off, q1); AFE_ST(R, att, 2, off, q2); AFE_ST(R, att, 3, off, q3);
@@ -924,7 +870,7 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
     }
     // ---- onboard-logic gate fired on this sub-step: IMU synthesis ----
     if (tick) {
-      if (LOGIC && SINGLE && AFE_LOGIC_LOADS_LATE) {
+      if (LOGIC && SINGLE) {
         __builtin_amdgcn_sched_barrier(0);   // or the scheduler hoists the loads back to the top, registers and all
         AFE_LOAD_LOGIC_STATE();
       }
@@ -969,7 +915,7 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
   }
 
   // ---- write back (in place: same lines this lane just read) ----
-  if (!(LOGIC && SINGLE && AFE_LOGIC_LOADS_LATE)) {
+  if (!(LOGIC && SINGLE)) {
     AFE_ST(R, pos, 0, off, px); AFE_ST(R, pos, 1, off, py); AFE_ST(R, pos, 2, off, pz);
     AFE_ST(R, vel, 0, off, vx); AFE_ST(R, vel, 1, off, vy); AFE_ST(R, vel, 2, off, vz);
     AFE_ST(R, att, 0, off, q0); AFE_ST(R, att, 1, off, q1); AFE_ST(R, att, 2, off, q2); AFE_ST(R, att, 3, off, q3);
@@ -1002,22 +948,17 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
 #undef AFE_STL
 }
 
-#ifndef AFE_LB_WAVES
-#define AFE_LB_WAVES 1
-#endif
-#ifndef AFE_BLOCK
-#define AFE_BLOCK 64    // threads per workgroup of the homogeneous-ensemble step kernel: one wave (measured: 64 < 128 < 256 < 512 in launch time)
-#endif
+constexpr int kStepBlock = 64;   // threads per workgroup of the homogeneous-ensemble step kernel: one wave (measured: 64 < 128 < 256 < 512 in launch time)
 
 // homogeneous ensemble: the one parameter record rides in the kernel arguments
 template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool SINGLE, bool BUF, int CP = 0>
-__global__ void __launch_bounds__(AFE_BLOCK, AFE_LB_WAVES)
+__global__ void __launch_bounds__(kStepBlock, 1)
 afe_step_kernel(const StepView<R> v, const DevParams<R> P, const DevLogic G) {
   // policy 3: workgroups are dealt to the eight XCDs round-robin (blockIdx % 8); XCD x takes the x-th contiguous eighth
   // of the launch, so each XCD's L2 -- and each memory channel group behind it -- streams ONE range instead of every
   // eighth line of all of them (the host asks for it only when the grid is a multiple of 8)
   const unsigned b = CP == 3 ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-  const int64_t i = v.first + (int64_t)b * AFE_BLOCK + threadIdx.x;
+  const int64_t i = v.first + (int64_t)b * kStepBlock + threadIdx.x;
   if (i >= v.end) return;
   run_vehicle<R, FEXT, TEXT, NOISE, LOGIC, SINGLE, BUF, false, (CP > 2 ? 2 : CP)>(v, P, G, i, v.tick_mask, v.n_steps, v.tick_base);
 }
@@ -1063,9 +1004,9 @@ afe_step_kernel_table(const StepView<R> v) {
 // scalar loads before anything is stored, and from there on the kernel is the homogeneous one (parameters
 // in scalar registers, one-wave workgroups, no LDS)
 template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool BUF>
-__global__ void __launch_bounds__(AFE_BLOCK, AFE_LB_WAVES)
+__global__ void __launch_bounds__(kStepBlock, 1)
 afe_step_kernel_wave_types(const StepView<R> v) {
-  const int64_t i = v.first + (int64_t)blockIdx.x * AFE_BLOCK + threadIdx.x;   // first is a multiple of 64: waves stay on aligned runs
+  const int64_t i = v.first + (int64_t)blockIdx.x * kStepBlock + threadIdx.x;   // first is a multiple of 64: waves stay on aligned runs
   if (i >= v.end) return;
   const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)v.type[i]);
   const DevParams<R> P = v.table[t];
@@ -1350,7 +1291,7 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
   // it was measured on at every size (tools/README.md).  Its counter-noise sibling gains the most where vector issue bounds
   // the step (262 144 vehicles 3.42 -> 2.60 us) but loses 3 % at 4 096 vehicles and 2 % at 2^20, and choosing by chunks
   // per worker at run time puts both bodies into one kernel, which spills to scratch; the others were not measured.
-  constexpr bool RELOADS = AFE_KERNARG_RELOAD && NOISE == 1 && persist_holds<R, FEXT, LOGIC, RESIDENT>();
+  constexpr bool RELOADS = NOISE == 1 && persist_holds<R, FEXT, LOGIC, RESIDENT>();
   u64_t s = a.start;
   u64_t t_wait = ticks100();
   u64_t tick_no = v.tick_base;                       // logic ticks so far (the counter policy's sample address)
@@ -1633,7 +1574,7 @@ static int launch_step(const StepView<R> &v, const LaunchFlags &f, const DevPara
   const int64_t count = v.end - v.first;
   if (count <= 0) return 0;
   const unsigned grid = (unsigned)((count + 255) / 256);
-  const unsigned grid_u = (unsigned)((count + AFE_BLOCK - 1) / AFE_BLOCK);
+  const unsigned grid_u = (unsigned)((count + kStepBlock - 1) / kStepBlock);
   const size_t lds = (size_t)v.n_types * (sizeof(DevParams<R>) + (f.logic ? sizeof(DevLogic) : 0));
   DevLogic no_logic = {};
   const DevLogic &G = uniform_logic ? *uniform_logic : no_logic;
@@ -1643,15 +1584,15 @@ static int launch_step(const StepView<R> &v, const LaunchFlags &f, const DevPara
       /* cache policy (LaunchFlags::cache_policy): buffer addressing, no external torque; otherwise the default kernel */ \
       constexpr bool CPOK = (BU) && !(TE);                                                                 \
       const int cp = !CPOK ? 0 : (f.cache_policy == 3 && (grid_u & 7u) ? 2 : f.cache_policy);             \
-      if (cp == 1) hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU, CPOK ? 1 : 0>), dim3(grid_u), dim3(AFE_BLOCK), 0, st, v, *uniform, G); \
-      else if (cp == 2) hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU, CPOK ? 2 : 0>), dim3(grid_u), dim3(AFE_BLOCK), 0, st, v, *uniform, G); \
-      else if (cp == 3) hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU, CPOK ? 3 : 0>), dim3(grid_u), dim3(AFE_BLOCK), 0, st, v, *uniform, G); \
-      else hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU>), dim3(grid_u), dim3(AFE_BLOCK), 0, st, v, *uniform, G); \
+      if (cp == 1) hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU, CPOK ? 1 : 0>), dim3(grid_u), dim3(kStepBlock), 0, st, v, *uniform, G); \
+      else if (cp == 2) hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU, CPOK ? 2 : 0>), dim3(grid_u), dim3(kStepBlock), 0, st, v, *uniform, G); \
+      else if (cp == 3) hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU, CPOK ? 3 : 0>), dim3(grid_u), dim3(kStepBlock), 0, st, v, *uniform, G); \
+      else hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, true, BU>), dim3(grid_u), dim3(kStepBlock), 0, st, v, *uniform, G); \
     }                                                                                                      \
     else if (uniform)                                                                                      \
-      hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, false, BU>), dim3(grid_u), dim3(AFE_BLOCK), 0, st, v, *uniform, G); \
-    else if (f.wave_uniform_types && AFE_BLOCK == 64)                                                      \
-      hipLaunchKernelGGL((afe_step_kernel_wave_types<R, FE, TE, NO, LO, BU>), dim3(grid_u), dim3(AFE_BLOCK), 0, st, v); \
+      hipLaunchKernelGGL((afe_step_kernel<R, FE, TE, NO, LO, false, BU>), dim3(grid_u), dim3(kStepBlock), 0, st, v, *uniform, G); \
+    else if (f.wave_uniform_types)                                                                         \
+      hipLaunchKernelGGL((afe_step_kernel_wave_types<R, FE, TE, NO, LO, BU>), dim3(grid_u), dim3(kStepBlock), 0, st, v); \
     else {                                                                                                 \
       /* a large type table (up to 256 records: 83 KB fp32 / 124 KB fp64 with the logic records) needs   \
          more than the default 64 KB of dynamic LDS; gfx950 has 160 KB per CU */                          \

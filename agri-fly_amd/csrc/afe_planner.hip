@@ -285,11 +285,8 @@ __device__ void unit_normal(const double a[3], const double b[3], double o[3]) {
 // (deproject: afe_planner.h)
 
 // shrink bookkeeping shared by the eight scans of DIP.cpp:617-940
-#ifndef AFE_SHRINK_QUAL
-#define AFE_SHRINK_QUAL            /* tools/planner_inline_probe.sh builds one variant with `volatile` here */
-#endif
 struct Shrink {
-  AFE_SHRINK_QUAL int right, left, top, bottom;
+  int right, left, top, bottom;
 };
 
 // NOTE on `noinline` below (build_mask, first_blocking_ring, side_scan, corner_scan, inflate_pyramid): with these
@@ -303,26 +300,10 @@ struct Shrink {
 // one cross-lane ordering this file relied on implicitly -- and with the helpers inlined again the campaign
 // still fails (plan 79 of 640: one candidate reported collision-free that is not).  So the barriers stay
 // because they are right, and `noinline` stays because it is needed.
-// Round 3 (tools/planner_inline_probe.sh, one helper force-inlined at a time): only side_scan's inlining breaks the
-// campaign, and only at the kernel's 128-VGPR budget -- the same source is correct at 168 or 256 VGPRs
-// (amdgpu_waves_per_eu 3 / 2).  The failing build is the one where the scans' wave-uniform state lives across vector
-// spills inside inflate_pyramid's divergent regions (planner section).
-// (each helper's attribute is a macro so that a build can inline them one at a time: tools/planner_inline_probe.sh)
-#ifndef AFE_NI_MASK
-#define AFE_NI_MASK __attribute__((noinline))
-#endif
-#ifndef AFE_NI_RING
-#define AFE_NI_RING __attribute__((noinline))
-#endif
-#ifndef AFE_NI_SIDE
-#define AFE_NI_SIDE __attribute__((noinline))
-#endif
-#ifndef AFE_NI_CORNER
-#define AFE_NI_CORNER __attribute__((noinline))
-#endif
-#ifndef AFE_NI_INFLATE
-#define AFE_NI_INFLATE __attribute__((noinline))
-#endif
+// Round 3 (tools/planner_inline_probe.sh in the history at 91979b1, one helper force-inlined at a time): only
+// side_scan's inlining breaks the campaign, and only at the kernel's 128-VGPR budget -- the same source is correct at
+// 168 or 256 VGPRs (amdgpu_waves_per_eu 3 / 2).  The failing build is the one where the scans' wave-uniform state lives
+// across vector spills inside inflate_pyramid's divergent regions (planner section).
 // ---- wave-cooperative pixel scans ------------------------------------------------
 // One wave runs one planner: everything outside the scans below is computed redundantly
 // (and therefore convergently) by all 64 lanes; inside a scan lane l looks at pixel
@@ -340,11 +321,7 @@ struct Shrink {
 // register and every decision made from it is a scalar branch).  The out-of-line helpers below take such values as
 // arguments -- which arrive in vector registers, "divergent" as far as the compiler can know; decisions made from them
 // inside loops whose other state is scalar were what the round-2 / round-3 `noinline` mystery came down to.
-#ifndef AFE_PLANNER_DIVERGENT_ARGS
 #define PL_UNIFORM(x) ((x) = __builtin_amdgcn_readfirstlane(x))
-#else
-#define PL_UNIFORM(x) ((void)0)
-#endif
 __device__ __forceinline__ int wave_min_i32(int v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(v, m); v = o < v ? o : v; }
@@ -382,7 +359,7 @@ constexpr int kSweepBatch = 8;
 // even that depth could not reach an edge any more.  (Images whose rows are not whole 64-pixel words, or too large for
 // the summaries' list in LDS; everything else goes through build_mask_sum below.)
 template <bool WANT_MIN>
-__device__ AFE_NI_MASK int build_mask(const uint16_t *__restrict__ img, int W, int H, int lane, uint64_t *mask, int WW, uint16_t lo,
+__device__ __attribute__((noinline)) int build_mask(const uint16_t *__restrict__ img, int W, int H, int lane, uint64_t *mask, int WW, uint16_t lo,
                           uint16_t hi) {
   PL_UNIFORM(W); PL_UNIFORM(H); PL_UNIFORM(WW);
   { int l = lo, h = hi; PL_UNIFORM(l); PL_UNIFORM(h); lo = (uint16_t)l; hi = (uint16_t)h; }
@@ -474,7 +451,7 @@ __device__ __forceinline__ void sum_list_flush(const uint4 *__restrict__ src, ui
 }
 
 template <bool WANT_MIN>
-__device__ AFE_NI_MASK int build_mask_sum(const uint16_t *__restrict__ img, const uint32_t *__restrict__ sums, int nwords, int lane,
+__device__ __attribute__((noinline)) int build_mask_sum(const uint16_t *__restrict__ img, const uint32_t *__restrict__ sums, int nwords, int lane,
                                           uint64_t *mask, uint16_t lo, uint16_t hi) {
   PL_UNIFORM(nwords);
   { int l = lo, h = hi; PL_UNIFORM(l); PL_UNIFORM(h); lo = (uint16_t)l; hi = (uint16_t)h; }
@@ -573,7 +550,7 @@ __device__ __forceinline__ bool mask_bit(const uint64_t *mask, int WW, int x, in
 // advancing.  The first ring in which a free side meets a marked pixel is therefore the smallest
 // ring distance of any marked pixel inside the window the free sides can still reach; all rings
 // before it are clear and can be taken in one step.  Returns that ring index (>= 1) or INT_MAX.
-__device__ AFE_NI_RING int first_blocking_ring(const uint64_t *mask, int WW, int lane, int xlo, int xhi, int ylo, int yhi, int L,
+__device__ __attribute__((noinline)) int first_blocking_ring(const uint64_t *mask, int WW, int lane, int xlo, int xhi, int ylo, int yhi, int L,
                                    int R, int T, int B) {
   PL_UNIFORM(WW); PL_UNIFORM(xlo); PL_UNIFORM(xhi); PL_UNIFORM(ylo); PL_UNIFORM(yhi); PL_UNIFORM(L); PL_UNIFORM(R); PL_UNIFORM(T); PL_UNIFORM(B);
   const int wa = xlo >> 6, nw = (xhi >> 6) - wa + 1, total = nw * (yhi - ylo + 1);
@@ -624,13 +601,10 @@ enum { SIDE_RIGHT = 0, SIDE_LEFT = 1, SIDE_TOP = 2, SIDE_BOTTOM = 3 };
 // Scans walk `total` pixels in chunks of 64; kScanBatch chunks are loaded together (the loads do
 // not depend on the edges) and then resolved one after the other, so one memory latency is paid
 // per batch instead of per chunk.  i / inner for i < 2^24, inner <= 2^15 as a multiply-high.
-#ifndef AFE_SCAN_BATCH
-#define AFE_SCAN_BATCH 4
-#endif
-constexpr int kScanBatch = AFE_SCAN_BATCH;
+constexpr int kScanBatch = 4;
 
 template <int SIDE>
-__device__ AFE_NI_SIDE bool side_scan(const uint16_t *__restrict__ src, int sx, int sy, const uint64_t *mask, int WW, int lane,
+__device__ __attribute__((noinline)) bool side_scan(const uint16_t *__restrict__ src, int sx, int sy, const uint64_t *mask, int WW, int lane,
                           int total, int inner, int xa, int ya, int dxo, int dyo, int dxi, int dyi, int num, int buf,
                           int x0, int y0, int dmin, Shrink &s) {
   PL_UNIFORM(sx); PL_UNIFORM(sy); PL_UNIFORM(WW); PL_UNIFORM(total); PL_UNIFORM(inner); PL_UNIFORM(xa); PL_UNIFORM(ya);
@@ -747,7 +721,7 @@ enum { CORNER_TR = 0, CORNER_BR = 1, CORNER_TL = 2, CORNER_BL = 3 };
 // One of the four corner scans, DIP.cpp:794-940: rows outward from the top / bottom edge,
 // pixels outward from the right / left edge.
 template <int CORNER>
-__device__ AFE_NI_CORNER bool corner_scan(const uint16_t *__restrict__ img, int W, const uint64_t *mask, int WW, int lane, int rows,
+__device__ __attribute__((noinline)) bool corner_scan(const uint16_t *__restrict__ img, int W, const uint64_t *mask, int WW, int lane, int rows,
                             int inner, int xa, int ya, int num, int buf, int x0, int y0, int dmin, Shrink &s) {
   constexpr bool RIGHT = (CORNER == CORNER_TR || CORNER == CORNER_BR);
   constexpr bool TOP = (CORNER == CORNER_TR || CORNER == CORNER_TL);
@@ -827,18 +801,17 @@ __device__ AFE_NI_CORNER bool corner_scan(const uint16_t *__restrict__ img, int 
 }
 
 // DIP.cpp:456-970, executed by one wave (lane = 0..63, everything but the scans is uniform)
-__device__ AFE_NI_INFLATE bool inflate_pyramid(const PlannerConfig &c, const uint16_t *__restrict__ img,
+__device__ __attribute__((noinline)) bool inflate_pyramid(const PlannerConfig &c, const uint16_t *__restrict__ img,
                                 const uint16_t *__restrict__ imgT, int HT, const uint32_t *__restrict__ sums, uint64_t *mask, int lane, int x0, int y0,
                                 double minimumDepth, PlannerPyramid &out) {
 #pragma clang fp contract(off)
   PL_COUNT(22, 1);
-#ifndef AFE_PLANNER_DIVERGENT_ARGS
   // Every lane of the wave holds the same seed pixel and depth, but as arguments of an out-of-line function they arrive
   // in vector registers and the compiler has to assume they differ: every decision made from them (the scans' "would this
   // cut the seed pixel off" tests, their `return false`) is then a DIVERGENT exit from loops whose other state -- the
   // edges, the ballot masks -- it keeps in scalar registers.  Saying that they are uniform makes those exits scalar
-  // branches.  (Round 4: this is what the failing build of round 2 / 3 depended on -- tools/planner_opt_bisect.sh,
-  // DESIGN.md planner section.)
+  // branches.  (Round 4: this is what the failing build of round 2 / 3 depended on -- tools/planner_opt_bisect.sh
+  // in the history at 91979b1, DESIGN.md planner section.)
   x0 = __builtin_amdgcn_readfirstlane(x0);
   y0 = __builtin_amdgcn_readfirstlane(y0);
   HT = __builtin_amdgcn_readfirstlane(HT);
@@ -847,7 +820,6 @@ __device__ AFE_NI_INFLATE bool inflate_pyramid(const PlannerConfig &c, const uin
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
     minimumDepth = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
   }
-#endif
   const int W = c.width, H = c.height, buf = c.pixel_buffer;
   const int edgeOff = (int)(c.focal_length * c.true_vehicle_radius / c.min_checking_dist);
   if (x0 <= edgeOff + buf + 1 || x0 > W - edgeOff - buf - 1 || y0 <= edgeOff + buf + 1 || y0 > H - edgeOff - buf - 1)
@@ -1307,12 +1279,10 @@ __global__ void __launch_bounds__(256) afe_rappids_candidates_kernel(const Plann
   b.cand_bits[t] = bits;
 }
 
-#ifndef AFE_PLANNER_WAVES
-#define AFE_PLANNER_WAVES 4
-#endif
+constexpr int kPlannerWaves = 4;   // waves per SIMD the search kernel is built for: a 128-VGPR budget
 // REGKEYS: at most 64 pyramids per plan -- the sorted list lives in the wave's lanes (PyrKeys)
 template <bool REGKEYS>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFE_PLANNER_WAVES, AFE_PLANNER_WAVES)))
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kPlannerWaves, kPlannerWaves)))
 afe_rappids_search_kernel(const PlannerConfig cfg, const PlannerBatch b) {
 #pragma clang fp contract(off)
   int64_t i = blockIdx.x;            // one wave per planner

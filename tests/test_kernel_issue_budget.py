@@ -2,7 +2,7 @@
 logic, one step> -- is bound by vector-instruction issue while its working set lives in the L2s (131 072 - 262 144 vehicles;
 at 2^20 the bytes set the step), and a scalar value the compiler cannot keep in a scalar register
 comes back through a v_readlane, a vector instruction.  The one-step grid therefore re-reads its constants from the
-kernel-argument segment in its loops (afe_kernels.hip, AFE_KERNARG_RELOAD) instead of keeping them alive across the poll
+kernel-argument segment in its loops (afe_kernels.hip, RELOADS in afe_step_persistent_kernel) instead of keeping them alive across the poll
 loop.  What that buys is visible in the code object's notes: .sgpr_spill_count was 165 before the change and is 90 in this
 build (no lane operation left inside the chunk loop).  Held here: below 165, not above 96 (this build's 90 rounded up to a
 multiple of 8), and still at most 80 vector registers, no scratch and the held inputs' 5 376 B of LDS.  Metadata only; read
