@@ -62,6 +62,23 @@ __device__ __forceinline__ void mat_vec(const M *A, R x, R y, R z, R &ox, R &oy,
   oz = fm(R(A[8]), z, fm(R(A[7]), y, R(A[6]) * x));
 }
 
+// The IMU mount, _R_inverse * v in float (Quadcopter_T.cpp:166,175; Vec3.hpp:201-210): every product and every sum
+// rounded, as the reference's build does and as rates_logic_tick spells its own products.  NOT the fused chain above: a
+// fused float product differs from the reference's by a float ulp wherever the mount is not the identity, the sample
+// goes through the onboard logic into the commands, and the fp64 engine's closed loop then follows the reference to
+// 1e-6 instead of 1e-9 (tests/test_gpu_step_matrix.py, fp64 logic cells on the table with tilted mounts).  With the
+// identity mount of every shipped type both forms give the same bits (signs of zero included: x + 0 * y either way).
+__device__ __forceinline__ void mount_vec(const float *A, float x, float y, float z, float &ox, float &oy, float &oz) {
+#pragma clang fp contract(off)
+  // one row after the other (the empty statements pin that order): left to itself the scheduler forms all nine products
+  // at once, and the six registers that takes put the fp32 one-step grid and table kernels with the logic over their budget
+  ox = (A[0] * x + A[1] * y) + A[2] * z;
+  asm volatile("" : "+v"(ox), "+v"(x), "+v"(y), "+v"(z));
+  oy = (A[3] * x + A[4] * y) + A[5] * z;
+  asm volatile("" : "+v"(oy), "+v"(x), "+v"(y), "+v"(z));
+  oz = (A[6] * x + A[7] * y) + A[8] * z;
+}
+
 // ---------------------------------------------------------------------------
 // IMU noise: std::minstd_rand0 + libstdc++ std::normal_distribution<double>
 // (reference Quadcopter_T.hpp:122-123; bits/random.tcc), always in double.
@@ -875,7 +892,7 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
         AFE_LOAD_LOGIC_STATE();
       }
       float tx_, ty_, tz_;
-      mat_vec<float>(P.Rimu, (float)wx, (float)wy, (float)wz, tx_, ty_, tz_);  // :165-166
+      mount_vec(P.Rimu, (float)wx, (float)wy, (float)wz, tx_, ty_, tz_);  // :165-166
       gx = tx_ + ng[0]; gy = ty_ + ng[1]; gz = tz_ + ng[2];                    // :167-170
       // _att.Inverse() * (acc + (0,0,9.81)) with the NEW attitude, :174
       R Rn[9];
@@ -884,7 +901,7 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
       const R bx = fm(Rn[6], sz, fm(Rn[3], sy, Rn[0] * sx));
       const R by = fm(Rn[7], sz, fm(Rn[4], sy, Rn[1] * sx));
       const R bz = fm(Rn[8], sz, fm(Rn[5], sy, Rn[2] * sx));
-      mat_vec<float>(P.Rimu, (float)bx, (float)by, (float)bz, tx_, ty_, tz_);  // :175
+      mount_vec(P.Rimu, (float)bx, (float)by, (float)bz, tx_, ty_, tz_);  // :175
       ax_m = tx_ + na[0]; ay_m = ty_ + na[1]; az_m = tz_ + na[2];              // :176-179
       have_imu = true;
       if (LOGIC) {

@@ -325,12 +325,18 @@ def logic_params_from_type(t, onboard_period):
 class ClosedLoopBatch:
     """n vehicles stepped by the oracle with the restated onboard rates logic in
     the loop: the sequence of Quadcopter_T::Run (physics, gate, IMU, logic.Run,
-    motor commands taking effect on the next step)."""
+    motor commands taking effect on the next step).
 
-    def __init__(self, batch, logic_params_list, onboard_period):
+    counter=dict(seed=..., first_global=...): the IMU noise of the AFE_SEED_COUNTER
+    policy (step_counter: the sample of tick k of global vehicle g is imu_normals(seed, g, k))
+    instead of the libstdc++ streams of Batch.step; the logic tick is the same."""
+
+    def __init__(self, batch, logic_params_list, onboard_period, counter=None):
         self.b = batch
         self.L = logic_lib()
         self.lp = logic_params_list
+        self.counter = None if counter is None else dict(seed=int(counter["seed"]), first_global=int(counter.get("first_global", 0)))
+        self.ticks_so_far = 0           # the ordinal of the next logic tick (counter policy: what addresses the sample)
         self.states = []
         for i in range(batch.n):
             s = OraLogicState()
@@ -345,8 +351,14 @@ class ClosedLoopBatch:
 
     def step(self, dt, ticks):
         for tick in ticks:
-            self.b.step(dt, 1, ticks=[int(tick)])
+            if self.counter is None:
+                self.b.step(dt, 1, ticks=[int(tick)])
+            else:
+                dt_us = int(round(dt * 1e6))
+                assert abs(dt_us * 1e-6 - dt) <= 1e-15, "the counter driver steps whole microseconds"
+                step_counter(self.b, dt_us, 1, [int(tick)], tick_base=self.ticks_so_far, **self.counter)
             if tick:
+                self.ticks_so_far += 1
                 for i, s in enumerate(self.states):
                     g = (C.c_float * 3)(*[float(self.b.gyro[k, i]) for k in range(3)])
                     self.L.ora_logic_tick(C.byref(self.lp[int(self.b.types[i])]), C.byref(s), g)

@@ -91,3 +91,83 @@ def test_step_batch_counter_only_changes_the_noise_and_the_force():
         z = ora.imu_normals(11, 100 + i, 42)          # the third tick of the call: 40, 41, 42
         want_g = d.gyro[:, i] + np.float32(0.1) * z[:3].astype(np.float32)
         assert np.array_equal(c.gyro[:, i], want_g.astype(np.float32))
+
+
+# ---- the closed loop on the counter policy (ClosedLoopBatch(counter=...)) ----
+
+MIXED_TYPES = (5, 1, 2, 4)
+STATE_FIELDS = ("pos", "vel", "att", "ang_vel", "motor_speed", "motor_cmd", "ext_force", "ext_torque", "rng")
+
+
+def mixed_closed_loop(n, sigma_gyro, sigma_acc, counter, period=1 / 500):
+    r = np.random.default_rng(5)
+    table = [ora.params_from_type(t) for t in MIXED_TYPES]
+    for p in table:
+        p.sigma_gyro, p.sigma_acc = sigma_gyro, sigma_acc
+    types = (np.arange(n) % len(MIXED_TYPES)).astype(np.uint8)
+    b = ora.Batch(n, table, types)
+    b.pos[:] = r.normal(0, 1, (3, n)); b.pos[2] += 40
+    b.vel[:] = r.normal(0, 1, (3, n))
+    q = r.normal(0, 1, (4, n)); b.att[:] = q / np.linalg.norm(q, axis=0)
+    b.ang_vel[:] = r.normal(0, 0.6, (3, n))
+    b.motor_speed[:] = 600 + r.uniform(0, 100, (4, n))
+    b.ext_force[:] = r.normal(0, 0.1, (3, n))
+    b.rng[:] = 1 + np.arange(n)
+    cl = ora.ClosedLoopBatch(b, [ora.logic_params_from_type(t, period) for t in MIXED_TYPES], period, counter=counter)
+    return cl, r.uniform(6, 13, n).astype(np.float32), r.normal(0, 1.5, (3, n)).astype(np.float32)
+
+
+def test_counter_closed_loop_without_noise_is_the_closed_loop():
+    """both sigmas 0: the loop advanced by step_counter is the loop advanced by Batch.step, bit for bit, over a mixed-type
+    batch, idle ticks and commanded ticks, and it counts its ticks"""
+    n = 24
+    ticks = np.array([0, 1, 0, 1, 0, 1, 0, 1, 0, 1], np.uint8)
+    loops = []
+    for counter in (None, dict(seed=9, first_global=1_000_003)):
+        cl, thrust, wdes = mixed_closed_loop(n, 0.0, 0.0, counter)
+        cl.step(1e-3, ticks[:2])
+        cl.set_rates_cmd(thrust, wdes)
+        cl.step(1e-3, ticks[2:])
+        loops.append(cl)
+    a, c = loops
+    assert c.ticks_so_far == int(ticks.sum())
+    for f in STATE_FIELDS + ("gyro", "acc"):
+        if f != "rng":
+            assert np.array_equal(getattr(a.b, f), getattr(c.b, f)), f
+    assert np.array_equal(c.b.rng, 1 + np.arange(n)) and (a.b.rng != c.b.rng).all()   # only the libstdc++ loop draws from the word
+    assert np.abs(a.b.motor_cmd).max() > 0                     # the loop is closed: the logic wrote commands
+
+
+def test_counter_closed_loop_hands_the_logic_the_counter_sample_of_the_tick():
+    """noise on: at tick k the gyro sample the logic receives is the noise-free sample of the same step plus
+    sigma * imu_normals(seed, global index, k)[:3] narrowed to float, and the commands are that sample's"""
+    import ctypes as C
+    n, seed, first, sg = 12, 0xabcdef0123, 1_000_003, 0.1
+    cl, thrust, wdes = mixed_closed_loop(n, sg, 0.2, dict(seed=seed, first_global=first))
+    twin, _, _ = mixed_closed_loop(n, 0.0, 0.0, None)            # the same physics with the noise off, re-seated before every step
+    cl.set_rates_cmd(thrust, wdes)
+    k = 0
+    for tick in (0, 1, 1, 0, 1, 0, 1):
+        for f in STATE_FIELDS:
+            getattr(twin.b, f)[:] = getattr(cl.b, f)
+        before = []
+        for s in cl.states:
+            c = ora.OraLogicState()
+            C.memmove(C.byref(c), C.byref(s), C.sizeof(ora.OraLogicState))
+            before.append(c)
+        cl.step(1e-3, [tick])
+        twin.b.step(1e-3, 1, ticks=[tick])
+        for f in ("pos", "vel", "att", "ang_vel", "motor_speed"):
+            assert np.array_equal(getattr(twin.b, f), getattr(cl.b, f)), f       # the noise touches the sample only
+        if not tick:
+            continue
+        for i in range(n):
+            z = ora.imu_normals(seed, first + i, k)
+            want = (twin.b.gyro[:, i] + np.float32(sg) * z[:3].astype(np.float32)).astype(np.float32)
+            assert np.array_equal(cl.b.gyro[:, i], want), (k, i)
+            g = (C.c_float * 3)(*[float(x) for x in want])
+            cl.L.ora_logic_tick(C.byref(cl.lp[int(cl.b.types[i])]), C.byref(before[i]), g)
+            assert [cl.b.motor_cmd[m, i] for m in range(4)] == [np.float32(before[i].motor_speed_cmd[m]) for m in range(4)], (k, i)
+        k += 1
+    assert cl.ticks_so_far == k == 4
+    assert np.array_equal(cl.b.rng, 1 + np.arange(n))            # the libstdc++ words do not move
