@@ -346,7 +346,11 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
   return ((uint64_t)hi << 32) | lo;
 }
-// i / inner for 0 <= i < 2^24, 1 <= inner <= 2^15 as a multiply-high
+// i / inner as a multiply-high, exact while i * inner < 2^32: with magic = floor(2^32 / inner) + 1 the product is
+// i / inner + i * e / (inner * 2^32), e = inner - 2^32 mod inner <= inner, and the quotient is right as long as that
+// last term stays below 1 / inner.  Every caller has i < width * height and inner <= max(width, height); the API
+// refuses images with width * height * max(width, height) > 2^32 (afe_planner_api.cpp), beyond which the quotient
+// comes out one too large (first at 9000 x 56: 501759 / 8960).
 __device__ __forceinline__ unsigned div_magic(int inner) { return (unsigned)(0x100000000ull / (unsigned)inner) + 1u; }
 __device__ __forceinline__ int div_small(int i, int inner, unsigned magic) {
   return inner == 1 ? i : (int)__umulhi((unsigned)i, magic);
@@ -600,7 +604,7 @@ enum { SIDE_RIGHT = 0, SIDE_LEFT = 1, SIDE_TOP = 2, SIDE_BOTTOM = 3 };
 // reference's "return false".
 // Scans walk `total` pixels in chunks of 64; kScanBatch chunks are loaded together (the loads do
 // not depend on the edges) and then resolved one after the other, so one memory latency is paid
-// per batch instead of per chunk.  i / inner for i < 2^24, inner <= 2^15 as a multiply-high.
+// per batch instead of per chunk.  i / inner as a multiply-high: exact for i * inner < 2^32 (div_small).
 constexpr int kScanBatch = 4;
 
 template <int SIDE>

@@ -105,6 +105,11 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
   // pixels with 24-bit arithmetic; device-resident images must allow 16-byte loads
   if ((int64_t)((cfg->width + 63) / 64) * cfg->height * 8 > 65536 || (int64_t)cfg->width * cfg->height >= (1 << 24))
     return AFE_ERR_OUT_OF_RANGE;
+  // the scans divide a pixel index i < width * height by a line length inner <= max(width, height) with a multiply-high
+  // (div_small, afe_planner.hip) that is exact while i * inner < 2^32: refuse the shapes that could leave that domain
+  // (9000 x 56, 12000 x 40, 16000 x 32 ... pass the two limits above and get a quotient one too large)
+  if ((int64_t)cfg->width * cfg->height * (cfg->width > cfg->height ? cfg->width : cfg->height) > ((int64_t)1 << 32))
+    return AFE_ERR_OUT_OF_RANGE;
   if (depth_on_device && ((uintptr_t)depth_images & 15u)) return AFE_ERR_INVALID_ARG;
   // CheckInputFeasibility bisects a candidate's duration until a section is shorter than min_section_time
   // (RapidTrajectoryGenerator.cpp:130-145); the kernel keeps the pending halves on a stack of 24 (input_feasible), which

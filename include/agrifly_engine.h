@@ -385,7 +385,10 @@ int afe_planner_samples(uint32_t seed, int width, int height, int n_candidates, 
  *   out[n]; flags [n][n_candidates] or NULL: TrajectoryTestResult bits per candidate
  *   (1 LowCost, 2 DynamicsFeasible, 4 VelocityAdmissible, 8 CollisionFree).
  * Image size: ceil(width/64) * height <= 8192 (one bit per pixel is kept in LDS;
- * e.g. 640x480, 1024x512), else AFE_ERR_OUT_OF_RANGE.
+ * e.g. 640x480, 1024x512), width * height < 2^24, and width * height *
+ * max(width, height) <= 2^32 (the scans' index division is exact up to there;
+ * e.g. 8192x64, 2048x256 pass, 9000x56 does not), else AFE_ERR_OUT_OF_RANGE --
+ * decided on the host before anything is allocated or launched.
  * cfg->min_section_time: the input-feasibility test halves a candidate's duration
  * until a section is shorter than this, and the kernel holds at most 24 pending
  * halves where the reference recurses without a limit.  So that no candidate can

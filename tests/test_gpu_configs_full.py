@@ -121,13 +121,16 @@ def test_config5_262144_vehicles_depth_raycast(ora):
 def test_config3_65536_vehicles_planner_in_the_loop(ora):
     """65 536 vehicles fly into the orchard; from t = 0.5 s every third offboard tick renders every
     vehicle's depth image from the engine's state and plans on it (images stay in HBM).  Whole-ensemble
-    properties every frame; on three frames a 12-vehicle subsample is checked against the oracle CHAIN:
+    properties every frame; on three frames a 14-vehicle subsample is checked against the oracle CHAIN:
     image == checker's render of the engine's pose, plan == checker's planner on that image with the same
     inputs; and the first 40 ms of closed-loop physics (rates logic on the device, per-vehicle noise
     streams seeded by global index) == the oracle's closed loop for a 64-vehicle subsample."""
     n = 65536
     rng = np.random.default_rng(8)
-    sub_plan = np.sort(rng.choice(n, 12, replace=False))
+    # ... and the two vehicles at the seam of the planner's image preparation (65 535 images per launch: 65 534 is the
+    # last image of the first launch, 65 535 the only one of the second)
+    sub_plan = np.unique(np.concatenate([rng.choice(n, 12, replace=False), [65534, 65535]]))
+    assert len(sub_plan) == 14
     sub_phys = np.sort(rng.choice(n, 64, replace=False))
     frames, phys = [], {}
 

@@ -12,8 +12,8 @@ from tests import truth_checker as tc
 afa = importlib.import_module("agri-fly_amd")
 pytestmark = pytest.mark.gpu
 
-SIZES = [(72, 40), (200, 150), (320, 240)]            # 72: not a multiple of 64
-N_RANDOM = {72: 40, 200: 24, 320: 12}
+SIZES = [(72, 40), (200, 150), (201, 151), (320, 240)]            # 72: not a multiple of 64; 201 x 151: odd in both
+N_RANDOM = {72: 40, 200: 24, 201: 24, 320: 12}
 SCALE = 10.0 / 256.0
 
 
