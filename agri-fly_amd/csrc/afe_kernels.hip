@@ -1309,6 +1309,11 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
   // the step (262 144 vehicles 3.42 -> 2.60 us) but loses 3 % at 4 096 vehicles and 2 % at 2^20, and choosing by chunks
   // per worker at run time puts both bodies into one kernel, which spills to scratch; the others were not measured.
   constexpr bool RELOADS = NOISE == 1 && persist_holds<R, FEXT, LOGIC, RESIDENT>();
+  // Which instantiations alternate the order of a worker's chunks from step to step (the comment at the chunk loop): the same
+  // one.  The order costs nothing by itself, the loop's shape does where the arguments live in scalar registers: the counter-noise
+  // sibling, measured with three shapes of the loop, lost 4-10 % at 4 096 - 262 144 vehicles (one chunk per worker, nothing
+  // to turn) against 5-12 % gained at 2^20 (tools/README.md); every other instantiation keeps the fixed order and its code.
+  constexpr bool TURNS = RELOADS;
   u64_t s = a.start;
   u64_t t_wait = ticks100();
   u64_t tick_no = v.tick_base;                       // logic ticks so far (the counter policy's sample address)
@@ -1337,7 +1342,8 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
     }
   }
   // fewer chunks than the most loaded worker by a quarter or more: time to spare in every step
-  const bool spare = 4 * ((a.n_chunks - w + a.n_workers - 1) / a.n_workers) <= 3 * ((a.n_chunks + a.n_workers - 1) / a.n_workers);
+  const int mine = (a.n_chunks - w + a.n_workers - 1) / a.n_workers;   // this worker's chunks: w, w + W, ... (the one division)
+  const bool spare = 4 * mine <= 3 * ((a.n_chunks + a.n_workers - 1) / a.n_workers);
   for (;;) {
     const u64_t idx = s + (u64_t)lane;
     const u64_t e = ld_agent(a.dev_ring + (idx & a.dev_mask));
@@ -1470,16 +1476,26 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
         }
         t_us += as.dt_us;
       }
-      for (int j = 0, c = w;; j++) {
+      // Where TURNS the worker takes its chunks forward in even steps, backward in odd ones (A B C | C B A | A B C ...): the
+      // last chunk of a step is the first of the next, so its state loads follow its own stores and are served by the L2
+      // (measured at 2^20 vehicles: 43 -> 34 B read per vehicle-step through the L2s' fabric side; the stores leave the L2
+      // all the same).  One chunk per worker has to stay: 6 143 x 3 328 B = 20 MB over the eight 4 MiB L2s.  Every load and
+      // store is still issued.  The parity is the absolute step's, so the order alternates across polls however many steps
+      // each one brings; j is the chunk's place with the worker -- its held-input slot -- in both directions.
+      const int dj = TURNS ? 1 - 2 * (int)(((unsigned)s + (unsigned)k) & 1u) : 1;
+      for (int j = TURNS && dj < 0 ? mine - 1 : 0, c = w;; j += dj) {
         const PersistKernarg<R> *const kc = RELOADS ? &persist_kernarg<R>() : nullptr;
         const StepView<R> &vc = RELOADS ? kc->v : v;
         const PersistArgs &ac = RELOADS ? kc->a : a;
-        if (c >= ac.n_chunks) break;
+        if (TURNS) {
+          if ((unsigned)j >= (unsigned)mine) break;                        // (past either end)
+          c = w + j * ac.n_workers;
+        } else if (c >= ac.n_chunks) break;
         const int64_t i = (int64_t)c * 64 + lane;
         if (i < vc.n)
           run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true, false, 0, HOLDS>(vc, RELOADS ? kc->P : P, RELOADS ? kc->G : G, i, tick, 1, tick_no,
                                                                                  HOLDS ? &held_lds[0] : nullptr, hold && j < AFE_PERSIST_HELD_SLOTS ? j : -1);
-        c += ac.n_workers;
+        if (!TURNS) c += ac.n_workers;
       }
       tick_no += tick;
     }
