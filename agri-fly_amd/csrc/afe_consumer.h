@@ -1,6 +1,6 @@
 // afe_consumer.h -- host plumbing shared by the library's consumers of the engine's device state and by the perception
 // entry points: depth camera (afe_render.hip), planner API (afe_planner_api.cpp), clearance query, contact monitor and path
-// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip).  Internal to the library, host only, header only.
+// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip).  Internal to the library, host only, header only.
 //
 //   engine_stream_device / engine_device_view / engine_shard   the engine's entry points for the library's other translation
 //                        units (implemented in afe_engine.cpp; afe_world.hip and afe_comm.cpp use the first and the last alone)
@@ -35,6 +35,22 @@ void engine_stream_device(afe_engine *e, void **stream, int *device);
 int engine_device_view(afe_engine *e, struct afe_device_view *out);
 // afe_engine.cpp: the engine's size, nothing touched
 void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);
+// afe_engine.cpp: the slabs afe_set_rates_commands writes (4 planar floats and one byte per vehicle, the engine's stride), for
+// the follower, which delivers on the device what that call uploads.  AFE_ERR_NOT_CONFIGURED without afe_set_rates_logic.
+// The caller has passed the gate (engine_enter) and launches on the engine's stream.
+int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd);
+
+// afe_planner_api.cpp: afe_rappids_plan_device for a caller whose planner inputs are in device memory already (planar [3][n]
+// doubles on `device`) and who takes the plans over there.  Nothing but the candidate table is uploaded; `out` and `flags`
+// are downloaded only where they are not NULL.  adopt(ctx, dev_out) runs after the planner's kernels have finished and while
+// the call still holds the planner's scratch: dev_out[n] is valid until it returns.
+struct PlanDeviceIO {
+  const double *vel0, *acc0, *grav, *cost_vec;
+  int (*adopt)(void *ctx, const afe_plan_output *dev_out);
+  void *ctx;
+};
+int plan_device_resident(int device, const afe_planner_config *cfg, int64_t n, const void *dev_depth_images, const double *samples,
+                         int n_candidates, const PlanDeviceIO &io, afe_plan_output *out, uint8_t *flags, float *kernel_ms);
 
 inline int pick_gfx950(int device, int *out) {
   int n_dev = 0;

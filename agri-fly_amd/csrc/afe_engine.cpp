@@ -1385,6 +1385,16 @@ extern "C" int afe_set_rates_commands(afe_engine *e, int64_t first, int64_t coun
   return fill_rows(e, e->have_cmd, 1, 1, first, count, 1);
 }
 
+extern "C" int afe_get_rates_commands(afe_engine *e, int64_t first, int64_t count, float *thrust_norm, float *ang_vel3, uint8_t *have) {
+  int rc = check_range(e, first, count);
+  if (rc) return rc;
+  if (!e->logic_on) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_rates_logic has not been called");
+  if (!thrust_norm && !ang_vel3 && !have) return fail(e, AFE_ERR_INVALID_ARG, "command arrays are NULL");
+  if ((rc = copy_out(e, e->rates_cmd, 4, 1, first, count, thrust_norm))) return rc;
+  if ((rc = copy_out(e, e->rates_cmd + e->stride, 4, 3, first, count, ang_vel3))) return rc;
+  return copy_out(e, e->have_cmd, 1, 1, first, count, have);
+}
+
 extern "C" int afe_set_commands_from_radio(afe_engine *e, int64_t first, int64_t count, const uint8_t *raw_packets) {
   int rc = check_range(e, first, count);
   if (rc) return rc;
@@ -1693,6 +1703,15 @@ void engine_stream_device(afe_engine *e, void **stream, int *device) {
 void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n) {
   *first_global = e->first_global;
   *n = e->n;
+}
+// (a host-visible arena's setters and getters go round the stream -- quiesce, then host copies --, so a kernel that
+// writes these slabs on the stream would not be ordered with them: refused)
+int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd) {
+  if (!e->logic_on) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_rates_logic has not been called");
+  if (e->host_arena) return fail(e, AFE_ERR_INVALID_ARG, "the follower needs an engine whose state is in device memory (afe_create)");
+  *rates_cmd = e->rates_cmd;
+  *have_cmd = e->have_cmd;
+  return AFE_OK;
 }
 // An asynchronous neighbour query may still be reading the gathered buffer and the world scratch: whatever is about to
 // rewrite them on the main stream is ordered behind it (a device-side wait; in steady state the query issued a cycle

@@ -95,9 +95,11 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
                      bool depth_on_device, int64_t n_images, const int32_t *image_index, const double *vel0,
                      const double *acc0, const double *grav, const double *cost_vec, const double *samples,
                      int n_tables, const int32_t *sample_table, int n_candidates, afe_plan_output *out,
-                     uint8_t *flags, float *kernel_ms) {
+                     uint8_t *flags, float *kernel_ms, const PlanDeviceIO *io = nullptr) {
+  // io: vel0, acc0, grav and cost_vec are in device memory already (nothing of them is uploaded), the plans are handed to
+  // io->adopt on the device, and `out` may be NULL (then it is not downloaded)
   if (!cfg || n < 0 || !depth_images || n_images <= 0 || !vel0 || !acc0 || !grav || !samples || n_tables <= 0 ||
-      n_candidates <= 0 || !out || cfg->max_pyramids <= 0 || cfg->width <= 0 || cfg->height <= 0)
+      n_candidates <= 0 || (!out && !io) || cfg->max_pyramids <= 0 || cfg->width <= 0 || cfg->height <= 0)
     return AFE_ERR_INVALID_ARG;
   if (!image_index && n_images < n) return AFE_ERR_INVALID_ARG;
   if (n == 0) return AFE_OK;             // (no planners: an empty request is answered)
@@ -134,12 +136,12 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
   const size_t px = (size_t)cfg->width * cfg->height;
   PooledBuf d_img(0), d_imgT(1), d_cc(2), d_cb(3), d_cs(4), d_idx(5), d_v(6), d_a(7), d_g(8), d_c(9), d_s(10), d_t(11), d_pyr(12), d_out(13),
       d_flags(14), d_resume(15), d_bins(16), d_sums(17), d_order(18);
-  if ((!depth_on_device && !d_img.upload(depth_images, (size_t)n_images * px * 2)) || !d_v.upload(vel0, (size_t)n * 24) ||
-      !d_a.upload(acc0, (size_t)n * 24) || !d_g.upload(grav, (size_t)n * 24) ||
+  if ((!depth_on_device && !d_img.upload(depth_images, (size_t)n_images * px * 2)) ||
+      (!io && (!d_v.upload(vel0, (size_t)n * 24) || !d_a.upload(acc0, (size_t)n * 24) || !d_g.upload(grav, (size_t)n * 24))) ||
       !d_s.upload(samples, (size_t)n_tables * n_candidates * 32))
     return AFE_ERR_HIP;
   if (image_index && !d_idx.upload(image_index, (size_t)n * 4)) return AFE_ERR_HIP;
-  if (cost_vec && !d_c.upload(cost_vec, (size_t)n * 24)) return AFE_ERR_HIP;
+  if (cost_vec && !io && !d_c.upload(cost_vec, (size_t)n * 24)) return AFE_ERR_HIP;
   if (sample_table && !d_t.upload(sample_table, (size_t)n * 4)) return AFE_ERR_HIP;
   if (!d_pyr.alloc((size_t)n * cfg->max_pyramids * sizeof(PlannerPyramid)) || !d_out.alloc((size_t)n * sizeof(PlanOutput)) ||
       !d_imgT.alloc((size_t)n_images * cfg->width * (size_t)((cfg->height + 63) / 64 * 64) * 2) || !d_cc.alloc((size_t)n * n_candidates * 8) ||
@@ -165,8 +167,8 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
   b.cand_sections = (CandSections *)d_cs.p;
   b.n_images = n_images;
   b.image_index = image_index ? (const int32_t *)d_idx.p : nullptr;
-  b.vel0 = (const double *)d_v.p; b.acc0 = (const double *)d_a.p; b.grav = (const double *)d_g.p;
-  b.cost_vec = cost_vec ? (const double *)d_c.p : nullptr;
+  b.vel0 = io ? vel0 : (const double *)d_v.p; b.acc0 = io ? acc0 : (const double *)d_a.p; b.grav = io ? grav : (const double *)d_g.p;
+  b.cost_vec = !cost_vec ? nullptr : io ? cost_vec : (const double *)d_c.p;
   b.samples = (const double *)d_s.p;
   b.sample_table = sample_table ? (const int32_t *)d_t.p : nullptr;
   b.n_candidates = n_candidates;
@@ -187,7 +189,11 @@ static int plan_impl(int device, const afe_planner_config *cfg, int64_t n, const
   const int rc = timer.finish(launch_rappids(*cfg, b, nullptr) == 0 ? AFE_OK : AFE_ERR_HIP, &ms);
   if (rc != AFE_OK) return rc;
   if (kernel_ms) *kernel_ms = ms;
-  if (hipMemcpy(out, d_out.p, (size_t)n * sizeof(PlanOutput), hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
+  if (io && io->adopt) {
+    const int arc = io->adopt(io->ctx, (const PlanOutput *)d_out.p);
+    if (arc != AFE_OK) return arc;
+  }
+  if (out && hipMemcpy(out, d_out.p, (size_t)n * sizeof(PlanOutput), hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
   if (flags && hipMemcpy(flags, d_flags.p, (size_t)n * n_candidates, hipMemcpyDeviceToHost) != hipSuccess) return AFE_ERR_HIP;
   return AFE_OK;
 }
@@ -209,4 +215,10 @@ extern "C" int afe_rappids_plan_device(int device, const afe_planner_config *cfg
                                        uint8_t *flags, float *kernel_ms) {
   return plan_impl(device, cfg, n, (const uint16_t *)dev_depth_images, true, n_images, image_index, vel0, acc0, grav,
                    cost_vec, samples, n_tables, sample_table, n_candidates, out, flags, kernel_ms);
+}
+
+int afe::plan_device_resident(int device, const afe_planner_config *cfg, int64_t n, const void *dev_depth_images, const double *samples,
+                              int n_candidates, const PlanDeviceIO &io, afe_plan_output *out, uint8_t *flags, float *kernel_ms) {
+  return plan_impl(device, cfg, n, (const uint16_t *)dev_depth_images, true, n, nullptr, io.vel0, io.acc0, io.grav, io.cost_vec, samples, 1,
+                   nullptr, n_candidates, out, flags, kernel_ms, &io);
 }

@@ -63,6 +63,11 @@ ABI_FUNCTIONS = [
     "afe_low_battery_threshold_from_type",
     "afe_raycast", "afe_raycast_stats", "afe_line_of_sight",
     "afe_range_sensor_create", "afe_range_sensor_update", "afe_range_sensor_info", "afe_range_sensor_destroy",
+    "afe_get_rates_commands",
+    "afe_follower_default_config", "afe_follower_ring_slots", "afe_follower_create", "afe_follower_destroy", "afe_follower_info",
+    "afe_follower_set_hold", "afe_follower_set_goal", "afe_follower_set_plans", "afe_follower_get_plans",
+    "afe_follower_planner_inputs", "afe_follower_plan", "afe_follower_tick", "afe_follower_get_reference",
+    "afe_follower_get_command", "afe_follower_selftest_math",
 ]
 
 
@@ -159,6 +164,14 @@ def plans_as_array(out):
     """zero-copy numpy view of the PlanOutput array rappids_plan returns"""
     assert PLAN_DTYPE.itemsize == C.sizeof(PlanOutput)
     return np.frombuffer(out, dtype=PLAN_DTYPE)
+
+
+class FollowerConfig(C.Structure):
+    """afe_follower_config (set struct_bytes before handing one to the library; follower_default_config does)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("period_us", C.c_uint64), ("delay_us", C.c_uint64),
+                ("lookahead_s", C.c_double), ("omega_step_s", C.c_double), ("mount", C.c_double * 4),
+                ("nat_freq", C.c_float), ("damping", C.c_float), ("att_time_const_xy", C.c_float),
+                ("att_time_const_z", C.c_float), ("hover_thrust", C.c_double)]
 
 
 class DeviceView(C.Structure):
@@ -423,6 +436,22 @@ def library():
         "afe_range_sensor_update": [vp, i64, i64, vp, vp, ci, C.POINTER(C.c_float)],
         "afe_range_sensor_info": [vp, C.POINTER(ci), C.POINTER(i64)],
         "afe_range_sensor_destroy": [vp],
+        "afe_get_rates_commands": [eng, i64, i64, vp, vp, vp],
+        "afe_follower_default_config": [ci, C.POINTER(FollowerConfig)],
+        "afe_follower_ring_slots": [u64, u64, C.POINTER(ci)],
+        "afe_follower_create": [eng, C.POINTER(FollowerConfig), C.POINTER(vp)],
+        "afe_follower_destroy": [vp],
+        "afe_follower_info": [vp, C.POINTER(i64), C.POINTER(ci), C.POINTER(u64), C.POINTER(ci)],
+        "afe_follower_set_hold": [vp, i64, i64, vp],
+        "afe_follower_set_goal": [vp, i64, i64, vp],
+        "afe_follower_set_plans": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp],
+        "afe_follower_get_plans": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp],
+        "afe_follower_planner_inputs": [vp, vp, vp, vp, vp],
+        "afe_follower_plan": [vp, C.POINTER(PlannerConfig), vp, vp, ci, vp, vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "afe_follower_tick": [vp, C.POINTER(i64)],
+        "afe_follower_get_reference": [vp, i64, i64, vp],
+        "afe_follower_get_command": [vp, i64, i64, vp, vp],
+        "afe_follower_selftest_math": [ci, ci, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1281,6 +1310,146 @@ class StatsMonitor:
             pass
 
 
+def follower_default_config(quadcopter_type):
+    """afe_follower_default_config: the tracking controller's tuning for the type and the loop's constants.  Pure host."""
+    c = FollowerConfig()
+    _status(library().afe_follower_default_config(int(quadcopter_type), C.byref(c)))
+    return c
+
+
+def follower_ring_slots(period_us, delay_us):
+    """afe_follower_ring_slots: slots of the delay ring.  Pure host."""
+    k = C.c_int()
+    _status(library().afe_follower_ring_slots(int(period_us), int(delay_us), C.byref(k)))
+    return k.value
+
+
+FOLLOWER_MATH_OPS = {"sinf": 0, "cosf": 1, "asinf": 2, "acosf": 3, "acos": 4}
+
+
+def follower_selftest_math(op, x, device=-1):
+    """afe_follower_selftest_math: the device library's sinf / cosf / asinf / acosf (float32) or acos (float64) of x, as
+    the follower's kernels call them; op is a name or 0..4"""
+    op = FOLLOWER_MATH_OPS.get(op, op)
+    a = np.ascontiguousarray(x, dtype=np.float64 if op == 4 else np.float32)
+    y = np.empty_like(a)
+    _status(library().afe_follower_selftest_math(int(device), int(op), a.size, a.ctypes.data, y.ctypes.data))
+    return y
+
+
+class Follower:
+    """afe_follower: plan adoption, tracking reference, tracking controller, radio codec and delay line for every vehicle
+    of an ensemble, on the device (see the header).  Borrows the ensemble: close the follower first."""
+
+    def __init__(self, ensemble, cfg=None, quadcopter_type=5):
+        self.cfg = follower_default_config(quadcopter_type) if cfg is None else cfg
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = ensemble
+        _status(library().afe_follower_create(ensemble.handle, C.byref(self.cfg), C.byref(self._h)))
+
+    def _range(self, first, count):
+        return int(first), int(self.n - first if count is None else count)
+
+    def set_hold(self, pos3, first=0):
+        p = np.ascontiguousarray(pos3, dtype=np.float64)
+        assert p.ndim == 2 and p.shape[0] == 3
+        _status(library().afe_follower_set_hold(self._h, int(first), p.shape[1], p.ctypes.data))
+
+    def set_goal(self, pos3, first=0):
+        p = np.ascontiguousarray(pos3, dtype=np.float64)
+        assert p.ndim == 2 and p.shape[0] == 3
+        _status(library().afe_follower_set_goal(self._h, int(first), p.shape[1], p.ctypes.data))
+
+    _PLAN_FIELDS = (("planned", np.uint8, 0), ("coeffs", np.float64, 18), ("tf", np.float64, 0), ("t_plan_us", np.uint64, 0),
+                    ("traj_att", np.float64, 4), ("offset", np.float64, 3), ("grav", np.float64, 3))
+
+    def set_plans(self, first=0, count=None, **fields):
+        """planned uint8 [count], coeffs [18, count] (row k = coeffs[k // 3][k % 3]), tf [count], t_plan_us uint64 [count],
+        traj_att [4, count], offset [3, count], grav [3, count]; what is not given stays as it is"""
+        first, count = self._range(first, count)
+        unknown = set(fields) - {k for k, _, _ in self._PLAN_FIELDS}
+        if unknown:
+            raise ValueError("unknown plan fields %r" % sorted(unknown))
+        keep, ptrs = [], []
+        for name, dtype, comps in self._PLAN_FIELDS:
+            if fields.get(name) is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(fields[name], dtype=dtype)
+            if a.shape != ((comps, count) if comps else (count,)):
+                raise ValueError("%s must have shape %r" % (name, (comps, count) if comps else (count,)))
+            keep.append(a)
+            ptrs.append(a.ctypes.data)
+        _status(library().afe_follower_set_plans(self._h, first, count, *ptrs))
+
+    def get_plans(self, first=0, count=None):
+        first, count = self._range(first, count)
+        out = {name: np.empty((comps, count) if comps else (count,), dtype) for name, dtype, comps in self._PLAN_FIELDS}
+        _status(library().afe_follower_get_plans(self._h, first, count, *[out[name].ctypes.data for name, _, _ in self._PLAN_FIELDS]))
+        return out
+
+    def planner_inputs(self):
+        """-> dict(vel0, acc0, grav, cost_vec), [3, n] each, formed on the device from the slabs"""
+        out = {k: np.empty((3, self.n)) for k in ("vel0", "acc0", "grav", "cost_vec")}
+        _status(library().afe_follower_planner_inputs(self._h, *[a.ctypes.data for a in out.values()]))
+        return out
+
+    def plan(self, cfg, depth_images, samples, want_out=False, want_flags=False):
+        """depth_images: a DeviceBuffer holding one image per vehicle (Scene.render_engine's).  -> (n_found, PlanOutput array
+        or None, flags or None, kernel_ms)"""
+        s = np.ascontiguousarray(samples, dtype=np.float64)
+        assert s.ndim == 2 and s.shape[1] == 4
+        out = (PlanOutput * self.n)() if want_out else None
+        flags = np.zeros((self.n, s.shape[0]), np.uint8) if want_flags else None
+        n_found, ms = C.c_int64(), C.c_float()
+        ptr = depth_images.ptr if isinstance(depth_images, DeviceBuffer) else depth_images
+        _status(library().afe_follower_plan(self._h, C.byref(cfg), ptr, s.ctypes.data, s.shape[0],
+                                            None if out is None else C.cast(out, C.c_void_p),
+                                            None if flags is None else flags.ctypes.data, C.byref(n_found), C.byref(ms)))
+        return n_found.value, out, flags, ms.value
+
+    def tick(self, count_tracking=False):
+        """one offboard period; -> vehicles on a running plan (count_tracking) or None (then nothing is downloaded)"""
+        if not count_tracking:
+            _status(library().afe_follower_tick(self._h, None))
+            return None
+        k = C.c_int64()
+        _status(library().afe_follower_tick(self._h, C.byref(k)))
+        return k.value
+
+    def get_reference(self, first=0, count=None):
+        """-> [14, count]: position 3, velocity 3, acceleration 3, thrust, body rates 3, running"""
+        first, count = self._range(first, count)
+        out = np.empty((14, count))
+        _status(library().afe_follower_get_reference(self._h, first, count, out.ctypes.data))
+        return out
+
+    def get_command(self, first=0, count=None):
+        """-> (computed [4, count], sent [4, count]) float32: thrust and body rates before and after the radio codec"""
+        first, count = self._range(first, count)
+        computed, sent = np.empty((4, count), np.float32), np.empty((4, count), np.float32)
+        _status(library().afe_follower_get_command(self._h, first, count, computed.ctypes.data, sent.ctypes.data))
+        return computed, sent
+
+    def info(self):
+        nv, sl, nt, fl = C.c_int64(), C.c_int(), C.c_uint64(), C.c_int()
+        _status(library().afe_follower_info(self._h, C.byref(nv), C.byref(sl), C.byref(nt), C.byref(fl)))
+        return {"n_vehicles": nv.value, "slots": sl.value, "n_ticks": nt.value, "in_flight": fl.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_follower_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def type_from_id(vehicle_id):
     return library().afe_type_from_id(int(vehicle_id))
 
@@ -1454,6 +1623,13 @@ class Ensemble:
             raise ValueError("thrust_norm must have shape (%d,)" % count)
         w, wp = _planar(ang_vel3, 3, count, np.float32)
         self._ck(self._L.afe_set_rates_commands(self._h, first, count, t.ctypes.data, wp))
+
+    def get_rates_commands(self, first=0, count=None):
+        """-> (thrust_norm [count], ang_vel [3, count]) float32, have [count] uint8: the rates command in force"""
+        first, count = self._range(first, count)
+        t, w, h = np.empty(count, np.float32), np.empty((3, count), np.float32), np.empty(count, np.uint8)
+        self._ck(self._L.afe_get_rates_commands(self._h, first, count, t.ctypes.data, w.ctypes.data, h.ctypes.data))
+        return t, w, h
 
     def set_commands_from_radio(self, raw_packets, first=0):
         """raw_packets: uint8 [count, 23]"""

@@ -290,6 +290,11 @@ int afe_set_rates_logic(afe_engine *e, const afe_rates_logic_params *table, int 
  * into EXTERNAL_RATES_CONTROL. */
 int afe_set_rates_commands(afe_engine *e, int64_t first, int64_t count,
                            const float *thrust_norm, const float *ang_vel3);
+/* The command in force (QuadcopterLogic's copy of the last externalRatesCmd, QuadcopterLogic.cpp:293-295): thrust_norm
+ * [count], ang_vel3 planar [3][count], have uint8 [count] (1: EXTERNAL_RATES_CONTROL, 0: IDLE).  Any may be NULL,
+ * not all. */
+int afe_get_rates_commands(afe_engine *e, int64_t first, int64_t count, float *thrust_norm, float *ang_vel3,
+                           uint8_t *have);
 /* The motor-speed commands currently in force (host- or logic-written). */
 int afe_get_motor_cmds(afe_engine *e, int64_t first, int64_t count, float *cmd4);
 
@@ -855,6 +860,104 @@ int afe_rappids_plan_device(int device, const afe_planner_config *cfg, int64_t n
                             const double *grav, const double *cost_vec, const double *samples, int n_tables,
                             const int32_t *sample_table, int n_candidates, afe_plan_output *out, uint8_t *flags,
                             float *kernel_ms);
+
+/* ---- trajectory follower ----------------------------------------------------
+ * The offboard side of the radio for a whole ensemble, on the device: what the
+ * Rappids_Simulator loop does between the planner's answer and the vehicle's
+ * command radio (Simulator/Rappids_Simulator/main.cpp:490-495,518-528,558-673,
+ * 737-739), one lane per vehicle, with the true state standing in for estState.
+ * A follower keeps per vehicle the adopted plan (the 18 coefficients of
+ * afe_plan_output::coeffs, its duration, when and in which frame it was
+ * planned), a hold position, a goal, previousThrust, the last command before
+ * and after the radio codec and the messages in flight.  Nothing of the state is
+ * downloaded: a tick reads the engine's slabs and writes the engine's rates
+ * command, with exactly the effect of afe_set_rates_commands.
+ * Every value is specified operation by operation in csrc/afe_follower.hip
+ * (tests/follower_checker.py restates it in numpy): IEEE arithmetic without
+ * contraction in the reference's order and precision -- double for the
+ * reference, float for the controller, Vec3f(double) narrowings where
+ * QuadcopterController.cpp has them -- so that everything but sinf, cosf, asinf,
+ * acosf and acos is reproducible to the bit on a host.
+ * Not covered: the mocap estimator and GetPrediction, ctrl.Run's take-off
+ * branch, the safety net, a desired yaw other than 0, delivery between ticks.
+ * Indices are engine-local.  The follower BORROWS the engine (destroy the
+ * follower first) and needs one whose state is in device memory (afe_create). */
+typedef struct afe_follower afe_follower;
+typedef struct afe_follower_config {
+  size_t struct_bytes;          /* IN: sizeof(afe_follower_config) as the caller was compiled; less is AFE_ERR_INVALID_ARG */
+  uint64_t period_us;           /* offboard period, main.cpp:175 (100 Hz): 10 000 */
+  uint64_t delay_us;            /* command radio delay, main.cpp:178,282-283: 30 000 */
+  double lookahead_s;           /* main.cpp:567: 0.04 */
+  double omega_step_s;          /* main.cpp:601: 0.02 */
+  double mount[4];              /* depthCamAtt, afe_camera_default_mount */
+  float nat_freq, damping;      /* posControl_natFreq, posControl_damping (QuadcopterConstants.hpp:34-35) */
+  float att_time_const_xy;      /* attControl_timeConst_xy, derived in float as QuadcopterConstants.hpp does */
+  float att_time_const_z;       /* attControl_timeConst_z: (0.04f * 5) * 2 = 0.399999976 for type 5, not 0.4f */
+  double hover_thrust;          /* reference thrust of a vehicle without a plan [m/s^2]: 9.81 */
+} afe_follower_config;
+
+/* QuadcopterController::SetParameters as main.cpp:227-229 calls it for the type (1, 2, 4, 5; else
+ * AFE_ERR_INVALID_ARG), and the loop's constants.  Pure host. */
+int afe_follower_default_config(int quadcopter_type, afe_follower_config *cfg);
+/* Slots of the delay ring: delay_us / period_us + 2 (the messages in flight at a tick, and the one being written).
+ * period_us == 0 and a result above 16: AFE_ERR_OUT_OF_RANGE.  Pure host. */
+int afe_follower_ring_slots(uint64_t period_us, uint64_t delay_us, int *slots);
+/* Nobody has a plan; hold and goal = where each vehicle is now; previousThrust = hover_thrust; nothing in flight.
+ * Needs afe_set_rates_logic (else AFE_ERR_NOT_CONFIGURED); a delay that needs more than 16 slots is AFE_ERR_OUT_OF_RANGE. */
+int afe_follower_create(afe_engine *e, const afe_follower_config *cfg, afe_follower **out);
+int afe_follower_destroy(afe_follower *f);   /* NULL is AFE_ERR_INVALID_ARG */
+/* (any output may be NULL) ticks so far, messages in flight after the last tick */
+int afe_follower_info(const afe_follower *f, int64_t *n_vehicles, int *slots, uint64_t *n_ticks, int *in_flight);
+
+/* desiredPosition of a vehicle without a plan (main.cpp:561-564) and the point the planner's cost pulls towards
+ * (ExplorationCost's direction: goal - position, in the camera frame), world frame, pos3 planar [3][count].
+ * count == 0 with a valid range is AFE_OK without touching the engine. */
+int afe_follower_set_hold(afe_follower *f, int64_t first, int64_t count, const double *pos3);
+int afe_follower_set_goal(afe_follower *f, int64_t first, int64_t count, const double *pos3);
+/* The adopted plans of vehicles [first, first+count), for a host-side planner to hand plans in and for read-back: planned
+ * uint8 [count], coeffs planar [18][count] (row k = coeffs[k / 3][k % 3]), tf [count], t_plan_us [count] (afe_time_us
+ * when it was planned: trackTrajTime.Reset()), traj_att4 planar [4][count] (trajAtt = att * depthCamAtt, main.cpp:520),
+ * offset3 (trajOffset, :523) and grav3 (gravity in the plan's frame, :494) planar [3][count].  An array that is NULL is
+ * left alone / not read back; all of them NULL is AFE_ERR_INVALID_ARG. */
+int afe_follower_set_plans(afe_follower *f, int64_t first, int64_t count, const uint8_t *planned, const double *coeffs,
+                           const double *tf, const uint64_t *t_plan_us, const double *traj_att4, const double *offset3,
+                           const double *grav3);
+int afe_follower_get_plans(afe_follower *f, int64_t first, int64_t count, uint8_t *planned, double *coeffs, double *tf,
+                           uint64_t *t_plan_us, double *traj_att4, double *offset3, double *grav3);
+
+/* The planner's inputs of every vehicle as they are now (main.cpp:490-495), formed on the device in double through the
+ * rotation matrix of Rotation.hpp:196-220 with camAtt = att * mount: vel0, acc0 (thrust previousThrust along body z,
+ * less gravity), grav and the goal vector, planar [3][n] each (any may be NULL, not all). */
+int afe_follower_planner_inputs(afe_follower *f, double *vel0, double *acc0, double *grav, double *cost_vec);
+/* main.cpp:484-528 for every vehicle: the inputs above, afe_rappids_plan_device on them without their leaving the device
+ * (image i for vehicle i, one candidate table samples[n_candidates][4]), and the adoption -- a vehicle whose planner
+ * found a trajectory takes its coefficients and duration, t_plan_us = afe_time_us, trajAtt = att * mount, trajOffset =
+ * position and the gravity vector, all as they stood for the inputs; the others keep what they had.  out[n] and flags
+ * [n][n_candidates] may be NULL (then they are not downloaded); n_found comes back as one 8-byte download. */
+int afe_follower_plan(afe_follower *f, const afe_planner_config *cfg, const void *dev_depth_images, const double *samples,
+                      int n_candidates, afe_plan_output *out, uint8_t *flags, int64_t *n_found, float *kernel_ms);
+
+/* One offboard period (main.cpp:558-673,737-739), once per period_us after afe_step; the caller keeps the 100 Hz gate.
+ * At now = afe_time_us, on the engine's stream (a resident step grid ends first): the tracking reference (:558-608),
+ * QuadcopterController::RunTracking (QuadcopterController.cpp:76-132), CreateRatesCommand and its decoding
+ * (RadioTypes.hpp:73-116,158-171,218-226) and CommunicationsDelay (CommunicationsDelay.hpp:18-33): the message is queued
+ * with due = now + delay_us, every message with due <= now is delivered in send order, and the newest of them is left
+ * in the engine's rates command exactly as afe_set_rates_commands would leave it.  Messages are delivered AT TICKS ONLY:
+ * one that falls due between two ticks (a delay that is no multiple of the period) waits for the next tick, where the
+ * reference looks at every simulation step.  n_tracking (may be NULL: then nothing is downloaded and the call does not
+ * wait): vehicles that are on a running plan.  A tick that would leave more messages in flight than the ring holds
+ * (ticks closer together than period_us) is AFE_ERR_OUT_OF_RANGE. */
+int afe_follower_tick(afe_follower *f, int64_t *n_tracking);
+
+/* What the last tick tracked and commanded.  ref14 planar [14][count]: position 3, velocity 3, acceleration 3, thrust,
+ * body rates 3, running (0 / 1).  computed4 / sent4 planar [4][count] (either may be NULL): thrust and body rates before
+ * and after the radio codec. */
+int afe_follower_get_reference(afe_follower *f, int64_t first, int64_t count, double *ref14);
+int afe_follower_get_command(afe_follower *f, int64_t first, int64_t count, float *computed4, float *sent4);
+/* Self-test hook: the device library's functions exactly as the follower's kernels call them, on GPU `device` (< 0:
+ * current).  op 0..3 = sinf, cosf, asinf, acosf (x, y float [n]); op 4 = acos (x, y double [n]).  With these values a
+ * host restatement reproduces every bit of a tick.  Replaces nothing in the reference. */
+int afe_follower_selftest_math(int device, int op, int64_t n, const void *x, void *y);
 
 /* ---- stepping -----------------------------------------------------------
  * afe_step replaces the loop body
