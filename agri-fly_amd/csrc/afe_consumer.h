@@ -1,6 +1,6 @@
 // afe_consumer.h -- host plumbing shared by the library's consumers of the engine's device state and by the perception
 // entry points: depth camera (afe_render.hip), planner API (afe_planner_api.cpp), clearance query, contact monitor and path
-// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip).  Internal to the library, host only, header only.
+// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip), mocap estimator (afe_estimator.hip).  Internal to the library, host only, header only.
 //
 //   engine_stream_device / engine_device_view / engine_shard   the engine's entry points for the library's other translation
 //                        units (implemented in afe_engine.cpp; afe_world.hip and afe_comm.cpp use the first and the last alone)
@@ -39,6 +39,9 @@ void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);
 // the follower, which delivers on the device what that call uploads.  AFE_ERR_NOT_CONFIGURED without afe_set_rates_logic.
 // The caller has passed the gate (engine_enter) and launches on the engine's stream.
 int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd);
+// afe_engine.cpp: AFE_ERR_INVALID_ARG for an engine whose state is host-visible (its setters go round the stream), for the
+// estimator, which like the follower works on the stream alone.  The caller has passed the gate.
+int engine_device_resident(afe_engine *e);
 
 // afe_planner_api.cpp: afe_rappids_plan_device for a caller whose planner inputs are in device memory already (planar [3][n]
 // doubles on `device`) and who takes the plans over there.  Nothing but the candidate table is uploaded; `out` and `flags`

@@ -1713,6 +1713,10 @@ int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd) {
   *have_cmd = e->have_cmd;
   return AFE_OK;
 }
+int engine_device_resident(afe_engine *e) {
+  if (e->host_arena) return fail(e, AFE_ERR_INVALID_ARG, "the estimator needs an engine whose state is in device memory (afe_create)");
+  return AFE_OK;
+}
 // An asynchronous neighbour query may still be reading the gathered buffer and the world scratch: whatever is about to
 // rewrite them on the main stream is ordered behind it (a device-side wait; in steady state the query issued a cycle
 // ago is long done and this costs nothing).

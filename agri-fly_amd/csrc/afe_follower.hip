@@ -62,6 +62,7 @@
 #include <vector>
 
 #include "afe_consumer.h"
+#include "afe_estimator.h"
 
 namespace {
 
@@ -503,8 +504,11 @@ __device__ __forceinline__ Command run_tracking(const Tuning &t, const V3 &pos, 
 
 // One offboard period: reference, controller, codec, delay line.  write_slot: where this tick's message goes;
 // deliver_slot: the newest message that is due (-1: none) -- it becomes the engine's rates command.
-template <typename T>
-__global__ void __launch_bounds__(kBlock) afe_follower_tick_kernel(FollowerArgs g, unsigned long long now_us, int write_slot, int deliver_slot) {
+// ANNOUNCE (an estimator is attached, and the state read is its prediction): SetPredictedValues(cmdAngVel, att * e3 * cmdThrust
+// - (0, 0, 9.81)), main.cpp:647-649, the doubles before any narrowing, into the estimator's ring slot `announce` (acc 3, angVel 3).
+template <typename T, bool ANNOUNCE>
+__global__ void __launch_bounds__(kBlock) afe_follower_tick_kernel(FollowerArgs g, unsigned long long now_us, int write_slot, int deliver_slot,
+                                                                   double *announce) {
 #pragma clang fp contract(off)
   const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t S = g.stride;
@@ -517,6 +521,14 @@ __global__ void __launch_bounds__(kBlock) afe_follower_tick_kernel(FollowerArgs 
     running = r.running;
     const Command c = run_tracking(g.tune, p, vel, q, r);
     g.prev_thrust[v] = c.thrust;
+    if (ANNOUNCE) {
+      V3 e3;
+      e3.x = 0.0; e3.y = 0.0; e3.z = 1.0;
+      const V3 up = m_rotate(q_matrix(q), e3);
+      double *A = announce + v;
+      A[0 * S] = up.x * c.thrust - 0.0; A[1 * S] = up.y * c.thrust - 0.0; A[2 * S] = up.z * c.thrust - 9.81;
+      A[3 * S] = c.ang_vel.x; A[4 * S] = c.ang_vel.y; A[5 * S] = c.ang_vel.z;
+    }
     float cmd[4], sent[4];
     cmd[0] = (float)c.thrust; cmd[1] = (float)c.ang_vel.x; cmd[2] = (float)c.ang_vel.y; cmd[3] = (float)c.ang_vel.z;
 #pragma unroll
@@ -595,13 +607,16 @@ struct afe_follower {
   uint64_t period_us = 0, delay_us = 0;
   uint64_t n_ticks = 0, seq = 0;    // seq: messages sent so far; message k lives in slot k % slots
   std::deque<uint64_t> due;         // due times of the messages in flight, in send order (the oldest is message seq - size)
+  afe_estimator *est = nullptr;     // borrowed; attached: the state read is its prediction, and a tick announces to it
   afe::DevBuf arena;
   FollowerArgs args;                // the follower's part of the kernel arguments
 };
 
 namespace {
 
-int enter(afe_follower *f, hipStream_t *stream, FollowerArgs *g, int *elem, bool want_cmd_slabs) {
+// estimated: the call reads estState -- with an estimator attached that is its prediction buffer, which looks like an fp64
+// engine's slabs with anchors of +0, so the <double> kernels read it as they read the truth
+int enter(afe_follower *f, hipStream_t *stream, FollowerArgs *g, int *elem, bool want_cmd_slabs, bool estimated = false) {
   afe::EngineAccess acc;
   const int rc = afe::engine_enter(f->engine, &acc);
   if (rc != AFE_OK) return rc;
@@ -612,6 +627,17 @@ int enter(afe_follower *f, hipStream_t *stream, FollowerArgs *g, int *elem, bool
   g->pos = view.pos; g->vel = view.vel; g->att = view.att;
   g->anchor_xy = view.pos_anchor_xy;
   *elem = view.state_elem_size;
+  if (estimated && f->est) {
+    uint64_t now_us = 0;
+    int rc = afe_time_us(f->engine, &now_us);
+    if (rc != AFE_OK) return rc;
+    afe::EstimatorLink link;
+    rc = afe::estimator_link(f->est, now_us, &link);
+    if (rc != AFE_OK) return rc;
+    g->pos = link.pos; g->vel = link.vel; g->att = link.att;
+    g->anchor_xy = link.zero_anchor_xy;
+    *elem = 8;
+  }
   if (want_cmd_slabs) return afe::engine_rates_slabs(f->engine, &g->rates_cmd, &g->have_cmd);
   return AFE_OK;
 }
@@ -864,7 +890,7 @@ extern "C" int afe_follower_planner_inputs(afe_follower *f, double *vel0, double
   hipStream_t stream = nullptr;
   FollowerArgs g;
   int elem = 0;
-  int rc = enter(f, &stream, &g, &elem, false);
+  int rc = enter(f, &stream, &g, &elem, false, true);
   if (rc != AFE_OK) return rc;
   rc = launch_inputs(g, elem, stream);
   if (rc != AFE_OK) return rc;
@@ -885,7 +911,7 @@ extern "C" int afe_follower_plan(afe_follower *f, const afe_planner_config *cfg,
   AdoptCtx ctx;
   ctx.f = f; ctx.n_found = 0;
   int elem = 0;
-  int rc = enter(f, &ctx.stream, &ctx.g, &elem, false);
+  int rc = enter(f, &ctx.stream, &ctx.g, &elem, false, true);
   if (rc != AFE_OK) return rc;
   uint64_t now_us = 0;
   rc = afe_time_us(f->engine, &now_us);
@@ -909,11 +935,16 @@ extern "C" int afe_follower_tick(afe_follower *f, int64_t *n_tracking) {
   hipStream_t stream = nullptr;
   FollowerArgs g;
   int elem = 0;
-  int rc = enter(f, &stream, &g, &elem, true);
+  int rc = enter(f, &stream, &g, &elem, true, true);
   if (rc != AFE_OK) return rc;
   uint64_t now_us = 0;
   rc = afe_time_us(f->engine, &now_us);
   if (rc != AFE_OK) return rc;
+  double *announce = nullptr, announce_from = 0;
+  if (f->est) {
+    rc = afe::estimator_announce_begin(f->est, now_us, &announce, &announce_from);
+    if (rc != AFE_OK) return rc;
+  }
   // the delay line's bookkeeping (CommunicationsDelay.hpp:18-33): this tick's message is sent, then every message that
   // is due is delivered in send order -- the newest of them is what the vehicle is left with
   size_t n_due = 0;
@@ -929,11 +960,16 @@ extern "C" int afe_follower_tick(afe_follower *f, int64_t *n_tracking) {
   } else g.counter = nullptr;
   if (f->n > 0) {
     rc = for_each_launch(g.n, [&](dim3 grid) {
-      if (elem == 8) hipLaunchKernelGGL(afe_follower_tick_kernel<double>, grid, dim3(kBlock), 0, stream, g, (unsigned long long)now_us, write_slot, deliver_slot);
-      else hipLaunchKernelGGL(afe_follower_tick_kernel<float>, grid, dim3(kBlock), 0, stream, g, (unsigned long long)now_us, write_slot, deliver_slot);
+      if (announce)
+        hipLaunchKernelGGL((afe_follower_tick_kernel<double, true>), grid, dim3(kBlock), 0, stream, g, (unsigned long long)now_us, write_slot, deliver_slot, announce);
+      else if (elem == 8)
+        hipLaunchKernelGGL((afe_follower_tick_kernel<double, false>), grid, dim3(kBlock), 0, stream, g, (unsigned long long)now_us, write_slot, deliver_slot, announce);
+      else
+        hipLaunchKernelGGL((afe_follower_tick_kernel<float, false>), grid, dim3(kBlock), 0, stream, g, (unsigned long long)now_us, write_slot, deliver_slot, announce);
     });
     if (rc != AFE_OK) return rc;
   }
+  if (f->est) afe::estimator_announce_commit(f->est, announce_from);
   for (size_t k = 0; k < n_due; k++) f->due.pop_front();
   if (!own_due) f->due.push_back(now_us + f->delay_us);
   f->seq++;
@@ -944,6 +980,16 @@ extern "C" int afe_follower_tick(afe_follower *f, int64_t *n_tracking) {
       return AFE_ERR_HIP;
     *n_tracking = (int64_t)tracking;
   }
+  return AFE_OK;
+}
+
+extern "C" int afe_follower_attach_estimator(afe_follower *f, afe_estimator *est) {
+  if (!f) return AFE_ERR_INVALID_ARG;
+  if (est) {
+    const int rc = afe::estimator_check_engine(est, f->engine);
+    if (rc != AFE_OK) return rc;
+  }
+  f->est = est;
   return AFE_OK;
 }
 

@@ -68,6 +68,9 @@ ABI_FUNCTIONS = [
     "afe_follower_set_hold", "afe_follower_set_goal", "afe_follower_set_plans", "afe_follower_get_plans",
     "afe_follower_planner_inputs", "afe_follower_plan", "afe_follower_tick", "afe_follower_get_reference",
     "afe_follower_get_command", "afe_follower_selftest_math",
+    "afe_estimator_default_config", "afe_estimator_ring_slots", "afe_estimator_create", "afe_estimator_destroy", "afe_estimator_info",
+    "afe_estimator_measure", "afe_estimator_predict", "afe_estimator_get_prediction", "afe_estimator_announce",
+    "afe_estimator_get_state", "afe_estimator_reset", "afe_estimator_selftest_math", "afe_follower_attach_estimator",
 ]
 
 
@@ -172,6 +175,13 @@ class FollowerConfig(C.Structure):
                 ("lookahead_s", C.c_double), ("omega_step_s", C.c_double), ("mount", C.c_double * 4),
                 ("nat_freq", C.c_float), ("damping", C.c_float), ("att_time_const_xy", C.c_float),
                 ("att_time_const_z", C.c_float), ("hover_thrust", C.c_double)]
+
+
+class EstimatorConfig(C.Structure):
+    """afe_estimator_config (estimator_default_config sets struct_bytes)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("command_delay_s", C.c_double), ("rate_time_constant_s", C.c_double),
+                ("gate", C.c_double), ("sigma_pos", C.c_double), ("sigma_att", C.c_double), ("sigma_acc", C.c_double),
+                ("sigma_ang_acc", C.c_double), ("offboard_period_us", C.c_uint64), ("max_measure_gap_us", C.c_uint64)]
 
 
 class DeviceView(C.Structure):
@@ -452,6 +462,19 @@ def library():
         "afe_follower_get_reference": [vp, i64, i64, vp],
         "afe_follower_get_command": [vp, i64, i64, vp, vp],
         "afe_follower_selftest_math": [ci, ci, i64, vp, vp],
+        "afe_estimator_default_config": [C.POINTER(EstimatorConfig)],
+        "afe_estimator_ring_slots": [C.POINTER(EstimatorConfig), C.POINTER(ci)],
+        "afe_estimator_create": [eng, C.POINTER(EstimatorConfig), C.POINTER(vp)],
+        "afe_estimator_destroy": [vp],
+        "afe_estimator_info": [vp, C.POINTER(i64), C.POINTER(ci), C.POINTER(u64), C.POINTER(ci), C.POINTER(C.c_uint32)],
+        "afe_estimator_measure": [vp, C.POINTER(i64)],
+        "afe_estimator_predict": [vp, C.c_double],
+        "afe_estimator_get_prediction": [vp, i64, i64, vp],
+        "afe_estimator_announce": [vp, i64, i64, vp, vp],
+        "afe_estimator_get_state": [vp, i64, i64, vp, vp, vp, vp, vp, vp],
+        "afe_estimator_reset": [vp, i64, i64],
+        "afe_estimator_selftest_math": [ci, ci, i64, vp, vp],
+        "afe_follower_attach_estimator": [vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1437,9 +1460,117 @@ class Follower:
         _status(library().afe_follower_info(self._h, C.byref(nv), C.byref(sl), C.byref(nt), C.byref(fl)))
         return {"n_vehicles": nv.value, "slots": sl.value, "n_ticks": nt.value, "in_flight": fl.value}
 
+    def attach_estimator(self, est):
+        """afe_follower_attach_estimator: plan, planner_inputs and tick read the estimator's prediction in place of the
+        truth, and a tick announces its command to it; None detaches.  Close the follower before the estimator."""
+        _status(library().afe_follower_attach_estimator(self._h, None if est is None else est._h))
+        self._est = est
+
     def close(self):
         if getattr(self, "_h", None):
             library().afe_follower_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
+            self._est = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def estimator_default_config():
+    """afe_estimator_default_config: MocapStateEstimator's statistics and the loop's cadences.  Pure host."""
+    c = EstimatorConfig()
+    _status(library().afe_estimator_default_config(C.byref(c)))
+    return c
+
+
+def estimator_ring_slots(cfg):
+    """afe_estimator_ring_slots: slots of the command ring for a configuration.  Pure host."""
+    k = C.c_int()
+    _status(library().afe_estimator_ring_slots(C.byref(cfg), C.byref(k)))
+    return k.value
+
+
+ESTIMATOR_MATH_OPS = {"sin": 0, "cos": 1, "asin": 2, "acos": 3, "exp": 4}
+
+
+def estimator_selftest_math(op, x, device=-1):
+    """afe_estimator_selftest_math: the device library's sin / cos / asin / acos / exp (float64) of x, as the estimator's
+    kernels call them; op is a name or 0..4"""
+    op = ESTIMATOR_MATH_OPS.get(op, op)
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(a)
+    _status(library().afe_estimator_selftest_math(int(device), int(op), a.size, a.ctypes.data, y.ctypes.data))
+    return y
+
+
+class Estimator:
+    """afe_estimator: Offboard::MocapStateEstimator and its PredictionPipe for every vehicle of an ensemble, on the device
+    (see the header).  Borrows the ensemble: close a follower it is attached to first, then the estimator."""
+
+    def __init__(self, ensemble, cfg=None):
+        self.cfg = estimator_default_config() if cfg is None else cfg
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = ensemble
+        _status(library().afe_estimator_create(ensemble.handle, C.byref(self.cfg), C.byref(self._h)))
+
+    def _range(self, first, count):
+        return int(first), int(self.n - first if count is None else count)
+
+    def measure(self, count_rejected=False):
+        """UpdateWithMeasurement(the engine's pose now); -> measurements rejected by this call (count_rejected) or None
+        (then nothing is downloaded and the call does not wait)"""
+        if not count_rejected:
+            _status(library().afe_estimator_measure(self._h, None))
+            return None
+        k = C.c_int64()
+        _status(library().afe_estimator_measure(self._h, C.byref(k)))
+        return k.value
+
+    def predict(self, ahead=0.03):
+        """GetPrediction(ahead) into the prediction buffer, stamped with the engine's time"""
+        _status(library().afe_estimator_predict(self._h, float(ahead)))
+
+    def prediction(self, first=0, count=None):
+        """-> [13, count]: position 3, velocity 3, attitude 4, body rates 3 of the last predict"""
+        first, count = self._range(first, count)
+        out = np.empty((13, count))
+        _status(library().afe_estimator_get_prediction(self._h, first, count, out.ctypes.data))
+        return out
+
+    def announce(self, ang_vel, acc, first=0):
+        """SetPredictedValues(ang_vel [3, count], acc [3, count]): one new message for the whole ensemble"""
+        w = np.ascontiguousarray(ang_vel, dtype=np.float64)
+        a = np.ascontiguousarray(acc, dtype=np.float64)
+        assert w.ndim == 2 and w.shape[0] == 3 and a.shape == w.shape
+        _status(library().afe_estimator_announce(self._h, int(first), w.shape[1], w.ctypes.data, a.ctypes.data))
+
+    def state(self, first=0, count=None):
+        """-> dict(est [13, count], cov [6, count] (P.vv, P.vr, P.rr, A.vv, A.vr, A.rr), valid_at_us, started,
+        rejected_in_a_row, rejected)"""
+        first, count = self._range(first, count)
+        out = {"est": np.empty((13, count)), "cov": np.empty((6, count)), "valid_at_us": np.empty(count, np.uint64),
+               "started": np.empty(count, np.uint8), "rejected_in_a_row": np.empty(count, np.uint32),
+               "rejected": np.empty(count, np.uint32)}
+        _status(library().afe_estimator_get_state(self._h, first, count, *[a.ctypes.data for a in out.values()]))
+        return out
+
+    def reset(self, first=0, count=None):
+        first, count = self._range(first, count)
+        _status(library().afe_estimator_reset(self._h, first, count))
+
+    def info(self):
+        nv, sl, nm, ng, er = C.c_int64(), C.c_int(), C.c_uint64(), C.c_int(), C.c_uint32()
+        _status(library().afe_estimator_info(self._h, C.byref(nv), C.byref(sl), C.byref(nm), C.byref(ng), C.byref(er)))
+        return {"n_vehicles": nv.value, "slots": sl.value, "n_measures": nm.value, "n_messages": ng.value, "error": er.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_estimator_destroy(self._h)
             self._h = C.c_void_p()
             self._keep = None
 

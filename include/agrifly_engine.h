@@ -865,7 +865,8 @@ int afe_rappids_plan_device(int device, const afe_planner_config *cfg, int64_t n
  * The offboard side of the radio for a whole ensemble, on the device: what the
  * Rappids_Simulator loop does between the planner's answer and the vehicle's
  * command radio (Simulator/Rappids_Simulator/main.cpp:490-495,518-528,558-673,
- * 737-739), one lane per vehicle, with the true state standing in for estState.
+ * 737-739), one lane per vehicle, with the true state standing in for estState
+ * unless an estimator is attached (afe_follower_attach_estimator).
  * A follower keeps per vehicle the adopted plan (the 18 coefficients of
  * afe_plan_output::coeffs, its duration, when and in which frame it was
  * planned), a hold position, a goal, previousThrust, the last command before
@@ -878,8 +879,8 @@ int afe_rappids_plan_device(int device, const afe_planner_config *cfg, int64_t n
  * reference, float for the controller, Vec3f(double) narrowings where
  * QuadcopterController.cpp has them -- so that everything but sinf, cosf, asinf,
  * acosf and acos is reproducible to the bit on a host.
- * Not covered: the mocap estimator and GetPrediction, ctrl.Run's take-off
- * branch, the safety net, a desired yaw other than 0, delivery between ticks.
+ * Not covered: ctrl.Run's take-off branch, the safety net, a desired yaw other
+ * than 0, delivery between ticks.
  * Indices are engine-local.  The follower BORROWS the engine (destroy the
  * follower first) and needs one whose state is in device memory (afe_create). */
 typedef struct afe_follower afe_follower;
@@ -958,6 +959,86 @@ int afe_follower_get_command(afe_follower *f, int64_t first, int64_t count, floa
  * current).  op 0..3 = sinf, cosf, asinf, acosf (x, y float [n]); op 4 = acos (x, y double [n]).  With these values a
  * host restatement reproduces every bit of a tick.  Replaces nothing in the reference. */
 int afe_follower_selftest_math(int device, int op, int64_t n, const void *x, void *y);
+
+/* ---- mocap state estimator ----------------------------------------------------
+ * Offboard::MocapStateEstimator with its PredictionPipe for a whole ensemble, on
+ * the device: what stands between the vehicle and the controller in the
+ * Rappids_Simulator loop (Simulator/Rappids_Simulator/main.cpp:451-457
+ * UpdateWithMeasurement at 200 Hz, :468-469 GetPrediction(0.03), :647-649
+ * SetPredictedValues after every controller run).  One constant-velocity filter
+ * for the position and one for the attitude per vehicle, propagated between
+ * measurements with the commands still in flight.  All double.  Every value is
+ * specified by cli/mocap_estimator.hpp line by line (csrc/afe_estimator.hip
+ * says how; tests/estimator_checker.py restates it in numpy): IEEE arithmetic
+ * without contraction, so that everything but sin, cos, asin, acos and exp is
+ * reproducible to the bit on a host.  The reference's own class drops into the
+ * same three calls: measure = UpdateWithMeasurement(truth pos, truth att),
+ * predict = GetPrediction(ahead), announce = SetPredictedValues.
+ * All times are relative to afe_time_us at creation.  The commands in flight are
+ * a ring of at most 16 messages for the whole ensemble (every vehicle is
+ * announced to in the same call); csrc/afe_estimator_ring.h states its rule.
+ * Indices are engine-local.  The estimator BORROWS the engine and needs one whose
+ * state is in device memory.  Destroy order: follower, estimator, engine. */
+typedef struct afe_estimator afe_estimator;
+typedef struct afe_estimator_config {
+  size_t struct_bytes;          /* IN: sizeof(afe_estimator_config) as the caller was compiled; less is AFE_ERR_INVALID_ARG */
+  double command_delay_s;       /* an announced command is active this much later (main.cpp:178): 0.03 */
+  double rate_time_constant_s;  /* the body rates relax towards the command with it (MocapStateEstimator.cpp:24-33): 0.04 */
+  double gate;                  /* measurement gate in standard deviations (:181-205): 6 */
+  double sigma_pos;             /* measurement noise, position [m]: 0.02 */
+  double sigma_att;             /* measurement noise, attitude [rad]: 5 pi / 180 */
+  double sigma_acc;             /* process noise, acceleration [m/s^2]: 9.81 */
+  double sigma_ang_acc;         /* process noise, angular acceleration [rad/s^2]: 200 */
+  uint64_t offboard_period_us;  /* announces are this far apart: 10 000 */
+  uint64_t max_measure_gap_us;  /* measure calls are at most this far apart: 10 000 (the loop's are 5 000) */
+} afe_estimator_config;
+
+int afe_estimator_default_config(afe_estimator_config *cfg);   /* pure host */
+/* Slots of the command ring: (ceil(command_delay_s * 1e6) + 2 * max_measure_gap_us) / offboard_period_us + 3.  A period
+ * of 0 or a result above 16: AFE_ERR_OUT_OF_RANGE.  Pure host. */
+int afe_estimator_ring_slots(const afe_estimator_config *cfg, int *slots);
+/* Reset() for every vehicle at time 0 = afe_time_us now: not started, the zero state, the initial variances, no message. */
+int afe_estimator_create(afe_engine *e, const afe_estimator_config *cfg, afe_estimator **out);
+int afe_estimator_destroy(afe_estimator *est);   /* NULL is AFE_ERR_INVALID_ARG */
+/* (any output may be NULL) measure calls so far, messages in the ring, error: 1 once a propagation loop hit its trip cap
+ * of slots + 2 (it cannot with the ring's rule; every later call but this and destroy is then AFE_ERR_OUT_OF_RANGE) */
+int afe_estimator_info(const afe_estimator *est, int64_t *n_vehicles, int *slots, uint64_t *n_measures, int *n_messages,
+                       uint32_t *error);
+
+/* UpdateWithMeasurement(position, attitude as the engine holds them now) for every vehicle, on the engine's stream (a
+ * resident step grid ends first): the first measurement initialises; later ones propagate to now with the commands in
+ * flight, gate at `gate` sigma (a rejected measurement is counted and skipped; after ten in a row the filter is reset
+ * and takes the eleventh), update and symmetrise.  n_rejected (may be NULL: then nothing is downloaded and the call does
+ * not wait): measurements this call rejected. */
+int afe_estimator_measure(afe_estimator *est, int64_t *n_rejected);
+/* GetPrediction(ahead_s) for every vehicle into the estimator's prediction buffer, stamped with afe_time_us; the
+ * estimate itself does not change.  Does not wait. */
+int afe_estimator_predict(afe_estimator *est, double ahead_s);
+/* The last prediction, est13 planar [13][count]: position 3, velocity 3, attitude 4, body rates 3.  Without a
+ * prediction: AFE_ERR_NOT_CONFIGURED. */
+int afe_estimator_get_prediction(afe_estimator *est, int64_t first, int64_t count, double *est13);
+/* SetPredictedValues from host arrays (a host-side controller), planar [3][count] each: one new message for the WHOLE
+ * ensemble, active command_delay_s from now; vehicles outside [first, first+count) repeat the message before it (+0
+ * if there is none).  AFE_ERR_OUT_OF_RANGE, and nothing changes, if the activation time is not strictly later than the
+ * newest message's, or if the slot to be overwritten may still be needed (csrc/afe_estimator_ring.h). */
+int afe_estimator_announce(afe_estimator *est, int64_t first, int64_t count, const double *ang_vel3, const double *acc3);
+/* The filter as it stands: est13 as above, cov6 planar [6][count] (position filter vv, vr, rr, attitude filter vv, vr,
+ * rr; rv is vr), valid_at_us (the time the estimate is valid at), started, the rejections in a row and in all.  An
+ * array that is NULL is not read back; all of them NULL is AFE_ERR_INVALID_ARG. */
+int afe_estimator_get_state(afe_estimator *est, int64_t first, int64_t count, double *est13, double *cov6, uint64_t *valid_at_us,
+                            uint8_t *started, uint32_t *rejected_in_a_row, uint32_t *rejected);
+/* Reset() for vehicles [first, first+count) at the time of the call (the rejection counters stay).  Does not wait. */
+int afe_estimator_reset(afe_estimator *est, int64_t first, int64_t count);
+/* Self-test hook: the device library's double functions exactly as the estimator's kernels call them, on GPU `device`
+ * (< 0: current).  op 0..4 = sin, cos, asin, acos, exp; x, y double [n]. */
+int afe_estimator_selftest_math(int device, int op, int64_t n, const double *x, double *y);
+/* estState for the follower (main.cpp:468-469): while an estimator is attached (it must borrow the same engine, else
+ * AFE_ERR_INVALID_ARG; NULL detaches), afe_follower_planner_inputs, afe_follower_plan (inputs and adoption) and
+ * afe_follower_tick read position, velocity and attitude from the estimator's prediction buffer instead of the
+ * engine's slabs, and afe_follower_tick announces (cmdAngVel, R(estAtt) e3 cmdThrust - (0, 0, 9.81)) -- the doubles
+ * before any narrowing, main.cpp:647-649 -- into the estimator's ring, under announce's refusals.  A tick, plan or
+ * planner_inputs without a prediction stamped at the current afe_time_us is AFE_ERR_NOT_CONFIGURED. */
+int afe_follower_attach_estimator(afe_follower *f, afe_estimator *est);
 
 /* ---- stepping -----------------------------------------------------------
  * afe_step replaces the loop body
