@@ -39,6 +39,13 @@ void engine_shard(const afe_engine *e, int64_t *first_global, int64_t *n);
 // the follower, which delivers on the device what that call uploads.  AFE_ERR_NOT_CONFIGURED without afe_set_rates_logic.
 // The caller has passed the gate (engine_enter) and launches on the engine's stream.
 int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd);
+// afe_engine.cpp: what rates_logic_tick keeps, for the GPS + IMU estimator, which consumes the logic's own filtered gyro
+// (LowPassFilterSecondOrder::GetValue is ym1: rows 9-11 of *lpf, 12 planar floats with the engine's stride) and rotates the
+// accelerometer sample by the logic's mount matrix (logic_table[type].R, device memory, current after the last afe_step);
+// *period = float(logic period), *n_ticks = afe_logic_ticks.  AFE_ERR_NOT_CONFIGURED without afe_set_rates_logic.  The
+// caller has passed the gate and launches on the engine's stream.
+struct DevLogic;
+int engine_logic_filter(afe_engine *e, const float **lpf, const DevLogic **logic_table, float *period, uint64_t *n_ticks);
 // afe_engine.cpp: AFE_ERR_INVALID_ARG for an engine whose state is host-visible (its setters go round the stream), for the
 // estimator, which like the follower works on the stream alone.  The caller has passed the gate.
 int engine_device_resident(afe_engine *e);

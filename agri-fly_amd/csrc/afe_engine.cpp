@@ -1713,6 +1713,14 @@ int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd) {
   *have_cmd = e->have_cmd;
   return AFE_OK;
 }
+int engine_logic_filter(afe_engine *e, const float **lpf, const DevLogic **logic_table, float *period, uint64_t *n_ticks) {
+  if (!e->logic_on) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_rates_logic has not been called");
+  *lpf = e->lpf;
+  *logic_table = e->dev_logic_table;
+  *period = (float)e->logic_period;
+  *n_ticks = e->n_ticks;
+  return AFE_OK;
+}
 int engine_device_resident(afe_engine *e) {
   if (e->host_arena) return fail(e, AFE_ERR_INVALID_ARG, "the estimator needs an engine whose state is in device memory (afe_create)");
   return AFE_OK;

@@ -63,6 +63,7 @@
 
 #include "afe_consumer.h"
 #include "afe_estimator.h"
+#include "afe_gps_estimator.h"
 
 namespace {
 
@@ -608,6 +609,7 @@ struct afe_follower {
   uint64_t n_ticks = 0, seq = 0;    // seq: messages sent so far; message k lives in slot k % slots
   std::deque<uint64_t> due;         // due times of the messages in flight, in send order (the oldest is message seq - size)
   afe_estimator *est = nullptr;     // borrowed; attached: the state read is its prediction, and a tick announces to it
+  afe_gps_estimator *gps = nullptr; // borrowed; attached: the state read is its estimate, and nothing is announced
   afe::DevBuf arena;
   FollowerArgs args;                // the follower's part of the kernel arguments
 };
@@ -633,6 +635,17 @@ int enter(afe_follower *f, hipStream_t *stream, FollowerArgs *g, int *elem, bool
     if (rc != AFE_OK) return rc;
     afe::EstimatorLink link;
     rc = afe::estimator_link(f->est, now_us, &link);
+    if (rc != AFE_OK) return rc;
+    g->pos = link.pos; g->vel = link.vel; g->att = link.att;
+    g->anchor_xy = link.zero_anchor_xy;
+    *elem = 8;
+  }
+  if (estimated && f->gps) {                                   // EstGetState: GetCurrentEstimate(), no prediction ahead
+    uint64_t n_ticks = 0;
+    int rc = afe_logic_ticks(f->engine, &n_ticks);
+    if (rc != AFE_OK) return rc;
+    afe::EstimatorLink link;
+    rc = afe::gps_estimator_link(f->gps, n_ticks, &link);
     if (rc != AFE_OK) return rc;
     g->pos = link.pos; g->vel = link.vel; g->att = link.att;
     g->anchor_xy = link.zero_anchor_xy;
@@ -986,10 +999,22 @@ extern "C" int afe_follower_tick(afe_follower *f, int64_t *n_tracking) {
 extern "C" int afe_follower_attach_estimator(afe_follower *f, afe_estimator *est) {
   if (!f) return AFE_ERR_INVALID_ARG;
   if (est) {
+    if (f->gps) return AFE_ERR_INVALID_ARG;                    // one kind of estimator at a time
     const int rc = afe::estimator_check_engine(est, f->engine);
     if (rc != AFE_OK) return rc;
   }
   f->est = est;
+  return AFE_OK;
+}
+
+extern "C" int afe_follower_attach_gps_estimator(afe_follower *f, afe_gps_estimator *gps) {
+  if (!f) return AFE_ERR_INVALID_ARG;
+  if (gps) {
+    if (f->est) return AFE_ERR_INVALID_ARG;                    // one kind of estimator at a time
+    const int rc = afe::gps_estimator_check_engine(gps, f->engine);
+    if (rc != AFE_OK) return rc;
+  }
+  f->gps = gps;
   return AFE_OK;
 }
 

@@ -71,6 +71,9 @@ ABI_FUNCTIONS = [
     "afe_estimator_default_config", "afe_estimator_ring_slots", "afe_estimator_create", "afe_estimator_destroy", "afe_estimator_info",
     "afe_estimator_measure", "afe_estimator_predict", "afe_estimator_get_prediction", "afe_estimator_announce",
     "afe_estimator_get_state", "afe_estimator_reset", "afe_estimator_selftest_math", "afe_follower_attach_estimator",
+    "afe_gps_estimator_default_config", "afe_gps_estimator_create", "afe_gps_estimator_destroy", "afe_gps_estimator_info",
+    "afe_gps_estimator_imu", "afe_gps_estimator_measure", "afe_gps_estimator_get_state", "afe_gps_estimator_set_state",
+    "afe_gps_estimator_reset", "afe_gps_estimator_selftest_math", "afe_follower_attach_gps_estimator",
 ]
 
 
@@ -182,6 +185,13 @@ class EstimatorConfig(C.Structure):
     _fields_ = [("struct_bytes", C.c_size_t), ("command_delay_s", C.c_double), ("rate_time_constant_s", C.c_double),
                 ("gate", C.c_double), ("sigma_pos", C.c_double), ("sigma_att", C.c_double), ("sigma_acc", C.c_double),
                 ("sigma_ang_acc", C.c_double), ("offboard_period_us", C.c_uint64), ("max_measure_gap_us", C.c_uint64)]
+
+
+class GpsEstimatorConfig(C.Structure):
+    """afe_gps_estimator_config (gps_estimator_default_config sets struct_bytes)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("init_sigma_pos", C.c_double), ("init_sigma_vel", C.c_double),
+                ("init_sigma_att", C.c_double), ("sigma_acc", C.c_double), ("sigma_gyro", C.c_double), ("sigma_pos", C.c_double),
+                ("accel_lowpass_cutoff", C.c_float)]
 
 
 class DeviceView(C.Structure):
@@ -475,6 +485,17 @@ def library():
         "afe_estimator_reset": [vp, i64, i64],
         "afe_estimator_selftest_math": [ci, ci, i64, vp, vp],
         "afe_follower_attach_estimator": [vp, vp],
+        "afe_gps_estimator_default_config": [C.POINTER(GpsEstimatorConfig)],
+        "afe_gps_estimator_create": [eng, C.POINTER(GpsEstimatorConfig), C.POINTER(vp)],
+        "afe_gps_estimator_destroy": [vp],
+        "afe_gps_estimator_info": [vp, C.POINTER(i64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
+        "afe_gps_estimator_imu": [vp],
+        "afe_gps_estimator_measure": [vp, C.POINTER(i64)],
+        "afe_gps_estimator_get_state": [vp, i64, i64, vp, vp, vp, vp, vp, vp],
+        "afe_gps_estimator_set_state": [vp, i64, i64, vp, vp, vp],
+        "afe_gps_estimator_reset": [vp, i64, i64],
+        "afe_gps_estimator_selftest_math": [ci, ci, i64, vp, vp],
+        "afe_follower_attach_gps_estimator": [vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1466,12 +1487,19 @@ class Follower:
         _status(library().afe_follower_attach_estimator(self._h, None if est is None else est._h))
         self._est = est
 
+    def attach_gps_estimator(self, gps):
+        """afe_follower_attach_gps_estimator: plan, planner_inputs and tick read the GPS + IMU estimator's current estimate
+        in place of the truth and announce nothing; None detaches.  Close the follower before the estimator."""
+        _status(library().afe_follower_attach_gps_estimator(self._h, None if gps is None else gps._h))
+        self._gps = gps
+
     def close(self):
         if getattr(self, "_h", None):
             library().afe_follower_destroy(self._h)
             self._h = C.c_void_p()
             self._keep = None
             self._est = None
+            self._gps = None
 
     def __del__(self):
         try:
@@ -1571,6 +1599,94 @@ class Estimator:
     def close(self):
         if getattr(self, "_h", None):
             library().afe_estimator_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gps_estimator_default_config():
+    """afe_gps_estimator_default_config: GPSIMUStateEstimator's statistics and the logic's accelerometer cutoff.  Pure host."""
+    c = GpsEstimatorConfig()
+    _status(library().afe_gps_estimator_default_config(C.byref(c)))
+    return c
+
+
+GPS_ESTIMATOR_MATH_OPS = {"sin": 0, "cos": 1, "acosf": 2}
+
+
+def gps_estimator_selftest_math(op, x, device=-1):
+    """afe_gps_estimator_selftest_math: the device library's sin / cos (float64) and acosf (x narrowed to float32, the result
+    widened) as the GPS + IMU estimator's kernels call them; op is a name or 0..2"""
+    op = GPS_ESTIMATOR_MATH_OPS.get(op, op)
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(a)
+    _status(library().afe_gps_estimator_selftest_math(int(device), int(op), a.size, a.ctypes.data, y.ctypes.data))
+    return y
+
+
+class GpsEstimator:
+    """afe_gps_estimator: Offboard::GPSIMUStateEstimator for every vehicle of an ensemble, on the device (see the header).
+    Borrows the ensemble, which needs set_rates_logic: close a follower it is attached to first, then the estimator."""
+
+    def __init__(self, ensemble, cfg=None):
+        self.cfg = gps_estimator_default_config() if cfg is None else cfg
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = ensemble
+        _status(library().afe_gps_estimator_create(ensemble.handle, C.byref(self.cfg), C.byref(self._h)))
+
+    def _range(self, first, count):
+        return int(first), int(self.n - first if count is None else count)
+
+    def imu(self):
+        """Predict(acc, gyro) with the sample of the latest logic tick: once per tick, right behind it.  Does not wait."""
+        _status(library().afe_gps_estimator_imu(self._h))
+
+    def measure(self, count_reinitialised=False):
+        """UpdateWithMeasurement(the engine's position now); -> vehicles that took the singular branch in this call
+        (count_reinitialised) or None (then nothing is downloaded and the call does not wait)"""
+        if not count_reinitialised:
+            _status(library().afe_gps_estimator_measure(self._h, None))
+            return None
+        k = C.c_int64()
+        _status(library().afe_gps_estimator_measure(self._h, C.byref(k)))
+        return k.value
+
+    def state(self, first=0, count=None):
+        """-> dict(est [13, count], cov [81, count] row major, last_predict_us, last_update_us, initialized, num_resets)"""
+        first, count = self._range(first, count)
+        out = {"est": np.empty((13, count)), "cov": np.empty((81, count)), "last_predict_us": np.empty(count, np.uint64),
+               "last_update_us": np.empty(count, np.uint64), "initialized": np.empty(count, np.uint8),
+               "num_resets": np.empty(count, np.uint32)}
+        _status(library().afe_gps_estimator_get_state(self._h, first, count, *[a.ctypes.data for a in out.values()]))
+        return out
+
+    def set_state(self, est=None, cov=None, corr=None, first=0):
+        """est [13, count], cov [81, count], corr [3, count] (_lastMeasUpdateAttCorrection); None leaves a part as it is.
+        The vehicles are marked initialised."""
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (est, cov, corr)]
+        count = next(a.shape[1] for a in arrs if a is not None)
+        for a, comps in zip(arrs, (13, 81, 3)):
+            assert a is None or a.shape == (comps, count)
+        _status(library().afe_gps_estimator_set_state(self._h, int(first), count, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def reset(self, first=0, count=None):
+        first, count = self._range(first, count)
+        _status(library().afe_gps_estimator_reset(self._h, first, count))
+
+    def info(self):
+        nv, ni, nm, lt = C.c_int64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _status(library().afe_gps_estimator_info(self._h, C.byref(nv), C.byref(ni), C.byref(nm), C.byref(lt)))
+        return {"n_vehicles": nv.value, "n_imu": ni.value, "n_measures": nm.value, "last_tick": lt.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_gps_estimator_destroy(self._h)
             self._h = C.c_void_p()
             self._keep = None
 

@@ -1040,6 +1040,74 @@ int afe_estimator_selftest_math(int device, int op, int64_t n, const double *x, 
  * planner_inputs without a prediction stamped at the current afe_time_us is AFE_ERR_NOT_CONFIGURED. */
 int afe_follower_attach_estimator(afe_follower *f, afe_estimator *est);
 
+/* ---- GPS + IMU state estimator -------------------------------------------------
+ * Offboard::GPSIMUStateEstimator (Components/Components/Offboard/GPSIMUStateEstimator.cpp), the estimator the field
+ * node defaults to (QuadRappidsPlannerAndController/ExampleVehicleStateMachine.cpp:11, :419), for every vehicle of an
+ * ensemble on the device: nine states in double with a 9x9 covariance per vehicle.  The node feeds it in three places,
+ * and so does a host here:
+ *     afe_gps_estimator_imu       CallbackIMU (:68-77): Predict(acc, gyro) on every IMU message -- every logic tick
+ *                                 (Simulator/main.cpp:229, 500 Hz)
+ *     afe_gps_estimator_measure   CallbackGPSEstimator (:79-85): UpdateWithMeasurement(pos) at 100 Hz (:228); the
+ *                                 position is the engine's true one (Simulator/main.cpp:428-432 publishes the truth)
+ *     an attached follower        EstGetState (:816-817): GetCurrentEstimate(), no prediction ahead;
+ *                                 EstSetPredictedValues (:833-835) does nothing, so nothing is announced
+ * The offboard loop is  [step to the tick -> _imu] x 5 -> _measure -> [render -> plan] -> follower tick; nothing of the
+ * state or of the IMU sample leaves the device.  The sample is what the simulated vehicle's GetAccelerometer /
+ * GetRateGyro return (Quadcopter_T.hpp:75-82): the logic's mount-rotated, low-passed values (QuadcopterLogic.hpp:40-52,
+ * :71-77).  The gyro value is the engine's own filter output; the accelerometer goes through a filter the estimator
+ * keeps (cutoff accel_lowpass_cutoff, QuadcopterLogic.cpp:102), which starts at 0 at creation: it equals the reference
+ * vehicle's only if the estimator is created before the first logic tick.
+ * csrc/afe_gps_estimator.hip states the arithmetic (tests/gps_imu_reference.py restates the class line by line in scalar
+ * Python, tests/gps_estimator_checker.py in numpy): IEEE double, uncontracted, in a fixed order; only sin, cos and acosf
+ * are the device library's.  The reference class itself is not compiled anywhere here (it needs Eigen): the restatement
+ * is not pinned to it.  Times are relative to afe_time_us at creation.  Indices are engine-local.  The estimator BORROWS
+ * the engine and needs one whose state is in device memory and whose rates logic is on.  Destroy order: follower,
+ * estimator, engine. */
+typedef struct afe_gps_estimator afe_gps_estimator;
+typedef struct afe_gps_estimator_config {
+  size_t struct_bytes;          /* IN: sizeof(afe_gps_estimator_config) as the caller was compiled; less is AFE_ERR_INVALID_ARG */
+  double init_sigma_pos;        /* [m]     3            GPSIMUStateEstimator.cpp:21-27 */
+  double init_sigma_vel;        /* [m/s]   3 */
+  double init_sigma_att;        /* [rad]   10 pi / 180 */
+  double sigma_acc;             /* [m/s^2] 5 */
+  double sigma_gyro;            /* [rad/s] 0.1 */
+  double sigma_pos;             /* [m]     0.25 */
+  float accel_lowpass_cutoff;   /* [rad/s] 100          QuadcopterLogic.cpp:102 */
+} afe_gps_estimator_config;
+int afe_gps_estimator_default_config(afe_gps_estimator_config *cfg);   /* pure host */
+/* The constructor (:9-30, Reset() once: numResets 1) for every vehicle.  AFE_ERR_NOT_CONFIGURED without
+ * afe_set_rates_logic, AFE_ERR_INVALID_ARG for a host-visible engine. */
+int afe_gps_estimator_create(afe_engine *e, const afe_gps_estimator_config *cfg, afe_gps_estimator **out);
+int afe_gps_estimator_destroy(afe_gps_estimator *g);   /* NULL is AFE_ERR_INVALID_ARG */
+/* Pure host; any pointer may be NULL.  last_tick: the afe_logic_ticks value whose sample the last _imu consumed (0: none). */
+int afe_gps_estimator_info(const afe_gps_estimator *g, int64_t *n_vehicles, uint64_t *n_imu, uint64_t *n_measures, uint64_t *last_tick);
+/* Predict(acc, gyro) (:66-203) for every vehicle with the sample of the latest logic tick, at afe_time_us.  Every sample
+ * must be seen exactly once: AFE_ERR_NOT_CONFIGURED, with nothing changed, unless afe_logic_ticks is one more than at the
+ * previous _imu (the first call needs at least one tick); afe_steps_until_tick says how far to step.  Does not wait. */
+int afe_gps_estimator_imu(afe_gps_estimator *g);
+/* UpdateWithMeasurement(the engine's position now) (:206-258).  n_reinitialised: the vehicles that took the singular
+ * branch (:228-237) in this call; NULL: nothing is downloaded and the call does not wait. */
+int afe_gps_estimator_measure(afe_gps_estimator *g, int64_t *n_reinitialised);
+/* Planar [comps][count]: est13 (pos 3, vel 3, att 4, ang_vel 3), cov81 (row major, all 81 words: after a Predict the
+ * matrix is symmetric in value but not in bits), the times of the last Predict and of the last good update, initialized,
+ * numResets.  An array that is NULL is not read back; all of them NULL is AFE_ERR_INVALID_ARG. */
+int afe_gps_estimator_get_state(afe_gps_estimator *g, int64_t first, int64_t count, double *est13, double *cov81, uint64_t *last_predict_us,
+                                uint64_t *last_update_us, uint8_t *initialized, uint32_t *num_resets);
+/* For tests and resumption: the given arrays (NULL: left as it is; all NULL is AFE_ERR_INVALID_ARG) are written, corr3 being
+ * _lastMeasUpdateAttCorrection, and the vehicles are marked initialised. */
+int afe_gps_estimator_set_state(afe_gps_estimator *g, int64_t first, int64_t count, const double *est13, const double *cov81,
+                                const double *corr3);
+/* Reset() (:32-44) for vehicles [first, first+count) at the time of the call, and the accelerometer low-pass at 0.  Does not wait. */
+int afe_gps_estimator_reset(afe_gps_estimator *g, int64_t first, int64_t count);
+/* Self-test hook: the device library's functions exactly as the kernels call them, on GPU `device` (< 0: current).
+ * op 0 = sin, 1 = cos (double), 2 = acosf of x narrowed to float, widened to double; x, y double [n]. */
+int afe_gps_estimator_selftest_math(int device, int op, int64_t n, const double *x, double *y);
+/* While a GPS estimator is attached (it must borrow the same engine, else AFE_ERR_INVALID_ARG; NULL detaches; attaching
+ * one kind of estimator while the other kind is attached is AFE_ERR_INVALID_ARG), afe_follower_planner_inputs,
+ * afe_follower_plan and afe_follower_tick read position, velocity and attitude from its estimate, and announce nothing.
+ * Such a call is AFE_ERR_NOT_CONFIGURED unless the estimator has had an _imu at the current afe_logic_ticks. */
+int afe_follower_attach_gps_estimator(afe_follower *f, afe_gps_estimator *g);
+
 /* ---- stepping -----------------------------------------------------------
  * afe_step replaces the loop body
  *     for (v : vehicles) v->Run();  simTimer.AdvanceMicroSeconds(dt_us);
