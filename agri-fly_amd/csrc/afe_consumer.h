@@ -1,6 +1,6 @@
 // afe_consumer.h -- host plumbing shared by the library's consumers of the engine's device state and by the perception
 // entry points: depth camera (afe_render.hip), planner API (afe_planner_api.cpp), clearance query, contact monitor and path
-// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip), mocap estimator (afe_estimator.hip).  Internal to the library, host only, header only.
+// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip), mocap estimator (afe_estimator.hip), flight stage machine (afe_stages.hip).  Internal to the library, host only, header only.
 //
 //   engine_stream_device / engine_device_view / engine_shard   the engine's entry points for the library's other translation
 //                        units (implemented in afe_engine.cpp; afe_world.hip and afe_comm.cpp use the first and the last alone)

@@ -812,3 +812,10 @@ int afe::gps_estimator_link(afe_gps_estimator *est, uint64_t n_ticks, EstimatorL
   out->zero_anchor_xy = est->args.slab + kRowZero * S;
   return AFE_OK;
 }
+
+int afe::gps_estimator_last_update(afe_gps_estimator *est, const unsigned long long **t_update_us, uint64_t *origin_us) {
+  if (!est || !t_update_us || !origin_us) return AFE_ERR_INVALID_ARG;
+  *t_update_us = (const unsigned long long *)est->args.slab + kRowTUpdate * est->stride;
+  *origin_us = est->t0_us;
+  return AFE_OK;
+}

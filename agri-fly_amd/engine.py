@@ -74,6 +74,9 @@ ABI_FUNCTIONS = [
     "afe_gps_estimator_default_config", "afe_gps_estimator_create", "afe_gps_estimator_destroy", "afe_gps_estimator_info",
     "afe_gps_estimator_imu", "afe_gps_estimator_measure", "afe_gps_estimator_get_state", "afe_gps_estimator_set_state",
     "afe_gps_estimator_reset", "afe_gps_estimator_selftest_math", "afe_follower_attach_gps_estimator",
+    "afe_stages_default_config", "afe_stages_create", "afe_stages_destroy", "afe_stages_info", "afe_stages_set_desired_position",
+    "afe_stages_set_desired_yaw", "afe_stages_set_centre", "afe_stages_set_unsafe", "afe_stages_request", "afe_stages_set_warnings",
+    "afe_stages_tick", "afe_stages_get", "afe_stages_attach_gps_estimator", "afe_stages_selftest_math",
 ]
 
 
@@ -192,6 +195,30 @@ class GpsEstimatorConfig(C.Structure):
     _fields_ = [("struct_bytes", C.c_size_t), ("init_sigma_pos", C.c_double), ("init_sigma_vel", C.c_double),
                 ("init_sigma_att", C.c_double), ("sigma_acc", C.c_double), ("sigma_gyro", C.c_double), ("sigma_pos", C.c_double),
                 ("accel_lowpass_cutoff", C.c_float)]
+
+
+class StagesConfig(C.Structure):
+    """afe_stages_config (stages_default_config sets struct_bytes)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("period_us", C.c_uint64), ("delay_us", C.c_uint64),
+                ("nat_freq", C.c_float), ("damping", C.c_float), ("att_time_const_xy", C.c_float), ("att_time_const_z", C.c_float),
+                ("min_corner", C.c_double * 3), ("max_corner", C.c_double * 3), ("min_normal_height", C.c_double),
+                ("not_seen_timeout_s", C.c_double), ("spool_up_time_s", C.c_double), ("spool_up_thrust_by_weight", C.c_double),
+                ("takeoff_time_s", C.c_double), ("get_into_action_time_s", C.c_double), ("landing_speed", C.c_double),
+                ("traj_id", C.c_int)]
+
+
+class StagesFields(C.Structure):
+    """afe_stages_fields: where afe_stages_get writes (NULL: not read back)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("stage", C.c_void_p), ("last_stage", C.c_void_p), ("t0_us", C.c_void_p),
+                ("safety", C.c_void_p), ("ready", C.c_void_p), ("init_pos3", C.c_void_p), ("desired_pos3", C.c_void_p),
+                ("last_pos3", C.c_void_p), ("last_vel3", C.c_void_p), ("last_acc3", C.c_void_p), ("cmd_yaw", C.c_void_p),
+                ("computed4", C.c_void_p), ("sent4", C.c_void_p), ("msg_type", C.c_void_p)]
+
+
+AFE_STAGE_WAIT_FOR_START, AFE_STAGE_SPOOL_UP, AFE_STAGE_TAKEOFF, AFE_STAGE_FLIGHT, AFE_STAGE_LANDING, AFE_STAGE_COMPLETE, \
+    AFE_STAGE_EMERGENCY = range(7)
+AFE_SAFETY_NOT_SEEN, AFE_SAFETY_UNSAFE_POSITION, AFE_SAFETY_UPSIDE_DOWN_AND_LOW, AFE_SAFETY_USER_UNSAFE = 1, 2, 4, 8
+AFE_WARN_LOW_BATT = 0x01
 
 
 class DeviceView(C.Structure):
@@ -496,6 +523,20 @@ def library():
         "afe_gps_estimator_reset": [vp, i64, i64],
         "afe_gps_estimator_selftest_math": [ci, ci, i64, vp, vp],
         "afe_follower_attach_gps_estimator": [vp, vp],
+        "afe_stages_default_config": [ci, C.POINTER(StagesConfig)],
+        "afe_stages_create": [eng, C.POINTER(StagesConfig), C.POINTER(vp)],
+        "afe_stages_destroy": [vp],
+        "afe_stages_info": [vp, C.POINTER(i64), C.POINTER(ci), C.POINTER(u64), C.POINTER(ci)],
+        "afe_stages_set_desired_position": [vp, i64, i64, vp],
+        "afe_stages_set_desired_yaw": [vp, i64, i64, vp],
+        "afe_stages_set_centre": [vp, i64, i64, vp],
+        "afe_stages_set_unsafe": [vp, i64, i64],
+        "afe_stages_request": [vp, i64, i64, ci, ci],
+        "afe_stages_set_warnings": [vp, i64, i64, vp],
+        "afe_stages_tick": [vp, ci, ci, vp],
+        "afe_stages_get": [vp, i64, i64, C.POINTER(StagesFields)],
+        "afe_stages_attach_gps_estimator": [vp, vp],
+        "afe_stages_selftest_math": [ci, ci, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1499,6 +1540,125 @@ class Follower:
             self._h = C.c_void_p()
             self._keep = None
             self._est = None
+            self._gps = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stages_default_config(quadcopter_type):
+    """afe_stages_default_config: the field node's mission constants and the controller's tuning for the type.  Pure host."""
+    c = StagesConfig()
+    _status(library().afe_stages_default_config(int(quadcopter_type), C.byref(c)))
+    return c
+
+
+STAGES_MATH_OPS = {"sin": 0, "cos": 1, "sinf": 2, "cosf": 3, "asinf": 4, "acosf": 5}
+
+
+def stages_selftest_math(op, x, device=-1):
+    """afe_stages_selftest_math: the device library's sin / cos (float64) or sinf / cosf / asinf / acosf (float32) of x, as
+    the stage machine's kernel calls them; op is a name or 0..5"""
+    op = STAGES_MATH_OPS.get(op, op)
+    a = np.ascontiguousarray(x, dtype=np.float64 if op < 2 else np.float32)
+    y = np.empty_like(a)
+    _status(library().afe_stages_selftest_math(int(device), int(op), a.size, a.ctypes.data, y.ctypes.data))
+    return y
+
+
+class FlightStages:
+    """afe_stages: the field node's mission -- wait, spool up, take off, fly, land, idle -- with its safety net, position
+    controller, radio codec and delay line for every vehicle of an ensemble, on the device (see the header).  Borrows the
+    ensemble and an attached estimator: close the stage machine first."""
+
+    _FIELDS = (("stage", np.uint8, 0), ("last_stage", np.uint8, 0), ("t0_us", np.uint64, 0), ("safety", np.uint8, 0),
+               ("ready", np.uint8, 0), ("init_pos", np.float64, 3), ("desired_pos", np.float64, 3), ("last_pos", np.float64, 3),
+               ("last_vel", np.float64, 3), ("last_acc", np.float64, 3), ("cmd_yaw", np.float64, 0), ("computed", np.float32, 4),
+               ("sent", np.float32, 4), ("msg_type", np.uint8, 0))
+
+    def __init__(self, ensemble, cfg=None, quadcopter_type=5):
+        self.cfg = stages_default_config(quadcopter_type) if cfg is None else cfg
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = ensemble
+        self._gps = None
+        _status(library().afe_stages_create(ensemble.handle, C.byref(self.cfg), C.byref(self._h)))
+
+    def _rows(self, a, comps, first):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        assert a.shape[:-1] == ((comps,) if comps else ())
+        return a, int(first), a.shape[-1]
+
+    def set_desired_position(self, pos3, first=0):
+        a, first, count = self._rows(pos3, 3, first)
+        _status(library().afe_stages_set_desired_position(self._h, first, count, a.ctypes.data))
+
+    def set_desired_yaw(self, yaw, first=0):
+        a, first, count = self._rows(yaw, 0, first)
+        _status(library().afe_stages_set_desired_yaw(self._h, first, count, a.ctypes.data))
+
+    def set_centre(self, xy2, first=0):
+        a, first, count = self._rows(xy2, 2, first)
+        _status(library().afe_stages_set_centre(self._h, first, count, a.ctypes.data))
+
+    def set_unsafe(self, first=0, count=None):
+        """SetExternalPanic for vehicles [first, first + count): userUnsafe, for good"""
+        _status(library().afe_stages_set_unsafe(self._h, int(first), int(self.n - first if count is None else count)))
+
+    def request(self, start=False, stop=False, first=0, count=None):
+        """the per-vehicle start / stop request that is OR-ed with a tick's arguments; it stays until changed"""
+        _status(library().afe_stages_request(self._h, int(first), int(self.n - first if count is None else count), int(bool(start)), int(bool(stop))))
+
+    def set_warnings(self, warnings, first=0):
+        w = np.ascontiguousarray(warnings, dtype=np.uint8)
+        assert w.ndim == 1
+        _status(library().afe_stages_set_warnings(self._h, int(first), w.size, w.ctypes.data))
+
+    def tick(self, should_start=False, should_stop=False, count=False):
+        """one period of Run(shouldStart, shouldStop); -> int64 [8]: vehicles per stage and the ready ones (count), or None
+        (then nothing is downloaded and the call does not wait)"""
+        if not count:
+            _status(library().afe_stages_tick(self._h, int(bool(should_start)), int(bool(should_stop)), None))
+            return None
+        c = np.zeros(8, np.int64)
+        _status(library().afe_stages_tick(self._h, int(bool(should_start)), int(bool(should_stop)), c.ctypes.data))
+        return c
+
+    def get(self, first=0, count=None, fields=None):
+        """-> dict of the machine's per-vehicle state (all of _FIELDS, or those named), planar [comps, count]"""
+        first = int(first)
+        count = int(self.n - first if count is None else count)
+        names = [f[0] for f in self._FIELDS] if fields is None else list(fields)
+        out, req = {}, StagesFields()
+        req.struct_bytes = C.sizeof(StagesFields)
+        for name, dtype, comps in self._FIELDS:
+            if name in names:
+                out[name] = np.empty((comps, count) if comps else (count,), dtype)
+                setattr(req, name + ("3" if comps == 3 else "4" if comps == 4 else ""), out[name].ctypes.data)
+        if len(out) != len(names):
+            raise ValueError("unknown fields %r" % sorted(set(names) - set(out)))
+        _status(library().afe_stages_get(self._h, first, count, C.byref(req)))
+        return out
+
+    def info(self):
+        nv, sl, nt, fl = C.c_int64(), C.c_int(), C.c_uint64(), C.c_int()
+        _status(library().afe_stages_info(self._h, C.byref(nv), C.byref(sl), C.byref(nt), C.byref(fl)))
+        return {"n_vehicles": nv.value, "slots": sl.value, "n_ticks": nt.value, "in_flight": fl.value}
+
+    def attach_gps_estimator(self, gps):
+        """afe_stages_attach_gps_estimator: a tick reads the GPS + IMU estimator's current estimate in place of the truth, and
+        the safety net its time since the last good measurement; None detaches.  Close the stage machine before the estimator."""
+        _status(library().afe_stages_attach_gps_estimator(self._h, None if gps is None else gps._h))
+        self._gps = gps
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().afe_stages_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
             self._gps = None
 
     def __del__(self):

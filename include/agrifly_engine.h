@@ -880,7 +880,7 @@ int afe_rappids_plan_device(int device, const afe_planner_config *cfg, int64_t n
  * QuadcopterController.cpp has them -- so that everything but sinf, cosf, asinf,
  * acosf and acos is reproducible to the bit on a host.
  * Not covered: ctrl.Run's take-off branch, the safety net, a desired yaw other
- * than 0, delivery between ticks.
+ * than 0 (the flight stage machine below has all three), delivery between ticks.
  * Indices are engine-local.  The follower BORROWS the engine (destroy the
  * follower first) and needs one whose state is in device memory (afe_create). */
 typedef struct afe_follower afe_follower;
@@ -1107,6 +1107,104 @@ int afe_gps_estimator_selftest_math(int device, int op, int64_t n, const double 
  * afe_follower_plan and afe_follower_tick read position, velocity and attitude from its estimate, and announce nothing.
  * Such a call is AFE_ERR_NOT_CONFIGURED unless the estimator has had an _imu at the current afe_logic_ticks. */
 int afe_follower_attach_gps_estimator(afe_follower *f, afe_gps_estimator *g);
+
+/* ---- flight stage machine -------------------------------------------------------
+ * The mission of the field node for a whole ensemble, on the device: ExampleVehicleStateMachine::Run of the GPS node
+ * (AIFS_ROS/hiperlab_rostools/src/QuadGPSRatesControl/ExampleVehicleStateMachine.cpp:106-379 with its main.cpp) -- wait, spool
+ * the motors up, take off, fly a demonstration trajectory, land, idle, exit -- with Offboard::SafetyNet
+ * (Components/Components/Offboard/SafetyNet.hpp) deciding every period whether a vehicle is killed, and the command from
+ * QuadcopterController::Run (QuadcopterController.cpp:11-74): the position controller with thrust saturation, a tilt floor
+ * and a commanded yaw, which the follower (RunTracking) does not cover.  Built like the follower: one lane per vehicle, planar
+ * slabs of its own, the engine's stream, the engine's rates-command slabs; nothing of the state is downloaded.
+ * csrc/afe_stages.hip states every value operation by operation in the reference's statement order -- the later assignment to
+ * the stage wins, so an unsafe vehicle whose spool-up time has passed goes to Takeoff, not Emergency; those overrides are the
+ * reference's and are kept.  tests/stage_machine_reference.py restates the three classes line by line in scalar Python,
+ * tests/stages_checker.py in numpy.  The class needs ROS and Eigen headers and is compiled nowhere here: the restatement is NOT
+ * pinned to the reference's binary.
+ * Two writers: a follower and a stage machine on one engine both write the rates command; the last writer's stands.
+ * The on-device logic has no sticky FS_KILLED: Emergency is never left and sends a kill every period, so the effect is the same.
+ * Not covered: the mocap node's variant of the class (the device mocap estimator keeps no last-good-measurement time and its
+ * announce ring needs per-stage rules), PublishEstimate's Euler angles, delivery between ticks, rappids_headless.
+ * Indices are engine-local.  The machine BORROWS the engine (and an attached estimator) and needs an engine whose state is in
+ * device memory and whose rates logic is on.  Destroy order: stage machine, estimator, engine. */
+enum {
+  AFE_STAGE_WAIT_FOR_START = 0, AFE_STAGE_SPOOL_UP = 1, AFE_STAGE_TAKEOFF = 2, AFE_STAGE_FLIGHT = 3, AFE_STAGE_LANDING = 4,
+  AFE_STAGE_COMPLETE = 5, AFE_STAGE_EMERGENCY = 6, AFE_STAGE_COUNT = 7    /* ExampleVehicleStateMachine.hpp:26-34 */
+};
+enum {                                    /* SafetyNet::SafetyState, one bit each */
+  AFE_SAFETY_NOT_SEEN = 1, AFE_SAFETY_UNSAFE_POSITION = 2, AFE_SAFETY_UPSIDE_DOWN_AND_LOW = 4, AFE_SAFETY_USER_UNSAFE = 8
+};
+#define AFE_WARN_LOW_BATT 0x01            /* TelemetryPacket.hpp:22 */
+typedef struct afe_stages afe_stages;
+typedef struct afe_stages_config {
+  size_t struct_bytes;          /* IN: sizeof(afe_stages_config) as the caller was compiled; less is AFE_ERR_INVALID_ARG */
+  uint64_t period_us;           /* mainLoopFrequency = 50 Hz: 20 000 */
+  uint64_t delay_us;            /* command radio delay: 30 000 */
+  float nat_freq, damping;      /* as afe_follower_default_config derives the four */
+  float att_time_const_xy, att_time_const_z;
+  double min_corner[3];         /* SetSafeCorners, ExampleVehicleStateMachine.cpp:88: (-100, -100, -2) */
+  double max_corner[3];         /* (100, 100, 20); a pair that is not ordered is AFE_ERR_INVALID_ARG (the reference asserts) */
+  double min_normal_height;     /* 0 */
+  double not_seen_timeout_s;    /* SafetyNet.hpp:57: 0.5 */
+  double spool_up_time_s;       /* :145: 0.5 */
+  double spool_up_thrust_by_weight; /* :146: 0.25 */
+  double takeoff_time_s;        /* :185: 2 */
+  double get_into_action_time_s;/* :222, :323: 2 */
+  double landing_speed;         /* :322: 0.5 m/s */
+  int traj_id;                  /* :219: 3 (0 fixed point, 1 circle, 2 SHM, 3 circle at fixed height, 4 circle with sinusoidal
+                                   height and yaw, 5 yaw at a fixed position); outside 0..5 is AFE_ERR_INVALID_ARG */
+} afe_stages_config;
+/* The reference's constants and the controller's parameters for the type (1, 2, 4, 5; else AFE_ERR_INVALID_ARG).  Pure host. */
+int afe_stages_default_config(int quadcopter_type, afe_stages_config *cfg);
+/* The constructor and Initialize for every vehicle: WaitForStart with last stage Complete, vehicleNotSeen set, desired position
+ * and yaw 0, the circle centre (0, -2) for traj_id 1 and (0, 0) otherwise, nothing in flight.  The ring follows
+ * afe_follower_ring_slots.  AFE_ERR_NOT_CONFIGURED without afe_set_rates_logic, AFE_ERR_INVALID_ARG for a host-visible engine. */
+int afe_stages_create(afe_engine *e, const afe_stages_config *cfg, afe_stages **out);
+int afe_stages_destroy(afe_stages *s);   /* NULL is AFE_ERR_INVALID_ARG */
+/* (any output may be NULL) ticks so far, messages in flight after the last tick */
+int afe_stages_info(const afe_stages *s, int64_t *n_vehicles, int *slots, uint64_t *n_ticks, int *in_flight);
+/* _desiredPosition (pos3 planar [3][count]), _desiredYawAngle (yaw [count]) and the circle centre's x and y of traj_id 1, 3, 4
+ * (xy2 planar [2][count]; the reference has one constant for all, an ensemble wants one per vehicle).  NULL is
+ * AFE_ERR_INVALID_ARG; count == 0 with a valid range is AFE_OK without touching the engine. */
+int afe_stages_set_desired_position(afe_stages *s, int64_t first, int64_t count, const double *pos3);
+int afe_stages_set_desired_yaw(afe_stages *s, int64_t first, int64_t count, const double *yaw);
+int afe_stages_set_centre(afe_stages *s, int64_t first, int64_t count, const double *xy2);
+/* SetExternalPanic -> SafetyNet::SetUnsafe: userUnsafe of the vehicles, for good. */
+int afe_stages_set_unsafe(afe_stages *s, int64_t first, int64_t count);
+/* A per-vehicle request that is OR-ed with the tick's shouldStart / shouldStop and stays until changed. */
+int afe_stages_request(afe_stages *s, int64_t first, int64_t count, int start, int stop);
+/* CallbackTelemetry's _lastTelWarnings, warnings [count]; HaveLowBattery() is bit AFE_WARN_LOW_BATT.  The simulated vehicle
+ * never reports a low battery by itself (Quadcopter_T.cpp:72 hands the logic 1.2 x the threshold). */
+int afe_stages_set_warnings(afe_stages *s, int64_t first, int64_t count, const uint8_t *warnings);
+/* Run(shouldStart, shouldStop) for every vehicle at now = afe_time_us, on the engine's stream (a resident step grid ends first):
+ * stage bookkeeping, state read (the engine's truth, or the attached estimator's estimate), safety net, the switch, Run, codec
+ * and delay line; the newest due message becomes the engine's rates command as afe_set_commands_from_radio would leave it
+ * (type 5: the four floats, have 1; idle and kill: zeros, have 0; WaitForStart's default message: nothing).  Messages are
+ * delivered AT TICKS ONLY.  counts8 (may be NULL: then nothing is downloaded and the call does not wait): vehicles per stage
+ * after the tick [0..6] and vehicles ready to exit [7]; GetIsReadyToExit of the ensemble is counts8[7] == n.  A tick that would
+ * leave more messages in flight than the ring holds is AFE_ERR_OUT_OF_RANGE. */
+int afe_stages_tick(afe_stages *s, int should_start, int should_stop, int64_t *counts8);
+/* What afe_stages_get reads back, planar [comps][count]; a pointer that is NULL is not read back, all NULL is AFE_ERR_INVALID_ARG. */
+typedef struct afe_stages_fields {
+  size_t struct_bytes;          /* IN: sizeof(afe_stages_fields) */
+  uint8_t *stage, *last_stage;  /* AFE_STAGE_* */
+  uint64_t *t0_us;              /* afe_time_us at the last stage timer reset */
+  uint8_t *safety;              /* AFE_SAFETY_* bits of the last tick */
+  uint8_t *ready;               /* _vehicleIsReadyForProgramToExit */
+  double *init_pos3, *desired_pos3, *last_pos3, *last_vel3, *last_acc3;
+  double *cmd_yaw;              /* _cmdYawAngle */
+  float *computed4, *sent4;     /* the last tick's command before and after the radio codec (zeros for types 0, 6, 2) */
+  uint8_t *msg_type;            /* its type: 0, 5 (rates), 6 (idle), 2 (kill) */
+} afe_stages_fields;
+int afe_stages_get(afe_stages *s, int64_t first, int64_t count, const afe_stages_fields *fields);
+/* While attached (the estimator must borrow the same engine, else AFE_ERR_INVALID_ARG; NULL detaches) a tick reads position,
+ * velocity and attitude from GetCurrentEstimate() and the safety net's time since the last good measurement from the estimator.
+ * Such a tick is AFE_ERR_NOT_CONFIGURED unless the estimator has had an _imu at the current afe_logic_ticks.  Without an
+ * estimator that time is 0: the truth is always seen. */
+int afe_stages_attach_gps_estimator(afe_stages *s, afe_gps_estimator *g);
+/* Self-test hook: the device library's functions exactly as the tick kernel calls them, through the same helpers, on GPU
+ * `device` (< 0: current).  op 0, 1 = sin, cos (x, y double [n]); op 2..5 = sinf, cosf, asinf, acosf (x, y float [n]). */
+int afe_stages_selftest_math(int device, int op, int64_t n, const void *x, void *y);
 
 /* ---- stepping -----------------------------------------------------------
  * afe_step replaces the loop body
