@@ -159,9 +159,12 @@ constexpr size_t persist_kernarg_bytes() { return offsetof(PersistKernarg<R>, a)
 #define AFE_PERSIST_SYNC_AREA_WORDS (16 * (AFE_PERSIST_SYNC_SHARDS + 3))   /* a pad line, 64 shard lines, the top line, slack */
 #define AFE_PERSIST_HOST_IO 0x10000u   /* PersistArgs::epoch */
 #define AFE_PERSIST_PRIO 0x20000u      /* PersistArgs::epoch: workers set their issue priority by the steps they have left (afe_kernels.hip) */
-#define AFE_PERSIST_HOLD 0x40000u      /* PersistArgs::epoch: nothing but this grid writes the commands and the force while it lives: the
-                                          instantiations that can (afe_kernels.hip, persist_holds) keep them in LDS */
-#define AFE_PERSIST_HELD_SLOTS 3       /* chunks per worker whose inputs a holding grid keeps in LDS (28 B x 64 lanes each) */
+#define AFE_PERSIST_HOLD 0x40000u      /* PersistArgs::epoch: nothing but this grid writes the commands and the force while it lives, and nothing
+                                          but this grid reads or writes the engine words: the instantiations that can (afe_kernels.hip,
+                                          persist_holds) keep the first two in LDS, the headline's the words in registers (written back
+                                          where a worker leaves the kernel) */
+#define AFE_PERSIST_HELD_SLOTS 3       /* chunks per worker whose inputs a holding grid keeps in LDS (28 B x 64 lanes each), and whose engine
+                                          words the headline's grid keeps in registers (HeldWords) */
 #define AFE_PERSIST_HOST_MARKS 64      /* host-visible arenas: grids of up to this many workers also write their marks to host_status[8 + w] */
 #define AFE_PERSIST_SYNC_WORD (8 + AFE_PERSIST_HOST_MARKS)      /* host_status: the step count the last sync request was answered for */
 #define AFE_PERSIST_SYNCREQ_WORD (9 + AFE_PERSIST_HOST_MARKS)   /* host_status: the host's sync request (a step count) */

@@ -583,6 +583,13 @@ int gust_resample(afe_engine *e, uint64_t epoch) {
 // written by the grid's own waves -- with two exceptions, which read them from memory as before: a host-visible arena
 // (the host writes the slabs in place beside a grid that stays, copy_in) and an exported device view (a writer the engine
 // does not know about).  DESIGN.md section 2 lists the writers.
+// The headline's grid (reference noise streams) holds the engine words of those chunks as well, in registers, and writes
+// them back to the `rng` slab where its workers leave the kernel (afe_kernels.hip HeldWords): while it lives the slab is
+// stale.  Sound for the same reason: every reader and writer of that slab on the host side -- afe_get_rng_state /
+// afe_set_rng_state, the checkpoints, afe_get_device_view, afe_set_imu_noise / afe_set_noise_seed, the launched steps -- comes
+// through main_stream, which ends the grid and waits for the kernel's end.  afe_sync leaves a grid resident and needs no
+// flush: nothing reads the slab behind it without one of those calls, and with an exported view or a host-visible arena
+// (where somebody could) nothing is held.
 bool persist_holds_inputs(const afe_engine *e, const LaunchFlags &f) {
   return e->precision == AFE_F32 && f.ext_force && !f.ext_torque && !f.logic && !f.resident && !e->view_exported && !e->host_arena;
 }

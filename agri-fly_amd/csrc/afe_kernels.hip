@@ -558,6 +558,14 @@ __device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t r, uint32_t voff, 
 struct HeldInputs {
   float v[AFE_PERSIST_HELD_SLOTS][7][64];
 };
+// ... and of their engine words (reference noise streams): one lane-private dword per slot, three named vector registers picked
+// by the wave-uniform slot (LDS has no room left at six waves per SIMD; an indexed array would live in scratch)
+struct HeldWords {
+  uint32_t w0, w1, w2;
+  __device__ __forceinline__ uint32_t get(int slot) const { return slot == 0 ? w0 : (slot == 1 ? w1 : w2); }
+  __device__ __forceinline__ void put(int slot, uint32_t x) { if (slot == 0) w0 = x; else if (slot == 1) w1 = x; else w2 = x; }
+};
+static_assert(AFE_PERSIST_HELD_SLOTS == 3, "HeldWords: one named register per held slot");
 
 // CP -- cache policy of the slab accesses (afe_set_cache_policy; memory hints only, never a different bit):
 //   0  default everywhere: an ensemble whose whole working set lives in the 256 MiB Infinity Cache (up to ~2^20 fp32 vehicles);
@@ -569,10 +577,13 @@ struct HeldInputs {
 //
 // HELD (the resident grid's one-step fp32 instantiations with an external force, persist_holds): the commands and the force
 // of a chunk the worker holds (held_slot >= 0, wave-uniform) come from the worker's LDS copy (HeldInputs), not from memory.
-template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool SINGLE, bool BUF, bool EACH = false, int CP = 0, bool HELD = false>
+// WORD (the headline's grid, reference noise streams): the engine word of a held chunk lives in a register of the worker
+// (HeldWords) from grid start to grid end; a tick takes it from there and leaves the advanced word there -- no load, no store.
+template <typename R, bool FEXT, bool TEXT, int NOISE, bool LOGIC, bool SINGLE, bool BUF, bool EACH = false, int CP = 0, bool HELD = false,
+          bool WORD = false>
 __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParams<R> &P, const DevLogic &G,
                                             const int64_t i, const unsigned long long tick_mask, const int n_steps_arg, const uint64_t tick_ordinal0,
-                                            const HeldInputs *held = nullptr, const int held_slot = -1) {
+                                            const HeldInputs *held = nullptr, const int held_slot = -1, HeldWords *held_words = nullptr) {
   // No implicit FMA contraction: every rounding is the one the source spells
   // out, so all instantiations (noise on/off, wrench on/off, table/uniform,
   // fused or single-step) produce bit-identical physics, and the operation
@@ -658,8 +669,13 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
     for (int m = 0; m < 4; m++) cmd_f[m] = held->v[held_slot][m][ln];
     fex = held->v[held_slot][4][ln]; fey = held->v[held_slot][5][ln]; fez = held->v[held_slot][6][ln];
   }
+  static_assert(!WORD || (HELD && NOISE == 1 && SINGLE), "held engine word: the one-step holding grid with the reference noise streams");
+  const bool word_held = WORD && held_slot >= 0;   // (wave-uniform)
   uint32_t rng = 0;
-  if (NOISE == 1 && tick_mask) rng = AFE_LD(uint32_t, rng, 0, off4);
+  if (NOISE == 1 && tick_mask) {
+    if (word_held) rng = held_words->get(held_slot);   // already here: the draws below wait for no round trip
+    else rng = AFE_LD(uint32_t, rng, 0, off4);
+  }
   uint64_t tick_ordinal = tick_ordinal0;   // NOISE == 2: the logic-tick number addresses the sample (wave-uniform)
   R px = AFE_LD(R, pos, 0, off), py = AFE_LD(R, pos, 1, off), pz = AFE_LD(R, pos, 2, off);
   R vx = AFE_LD(R, vel, 0, off), vy = AFE_LD(R, vel, 1, off), vz = AFE_LD(R, vel, 2, off);
@@ -725,6 +741,7 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
       // y <- 2, x <- 3.
       typename NormalOf<R>::type d[6];   // double in the fp64 engine, float in the fp32 engine
       six_normals(rng, d);
+      if (word_held) held_words->put(held_slot, rng);   // (one tick per call; the worker writes the words to the slab when it leaves)
       ng[0] = v.sigma_gyro * (float)d[2]; ng[1] = v.sigma_gyro * (float)d[1]; ng[2] = v.sigma_gyro * (float)d[0];
       na[0] = v.sigma_acc * (float)d[5]; na[1] = v.sigma_acc * (float)d[4]; na[2] = v.sigma_acc * (float)d[3];
     }
@@ -944,7 +961,9 @@ __device__ __forceinline__ void run_vehicle(const StepView<R> &v, const DevParam
   if (have_imu) {
     AFE_ST(float, gyro, 0, off4, gx); AFE_ST(float, gyro, 1, off4, gy); AFE_ST(float, gyro, 2, off4, gz);
     AFE_ST(float, acc, 0, off4, ax_m); AFE_ST(float, acc, 1, off4, ay_m); AFE_ST(float, acc, 2, off4, az_m);
-    if (NOISE == 1) AFE_ST(uint32_t, rng, 0, off4, rng);
+    if (NOISE == 1) {
+      if (!word_held) AFE_ST(uint32_t, rng, 0, off4, rng);
+    }
     if (LOGIC) {
 #pragma unroll
       for (int k = 0; k < 3; k++) {
@@ -1330,6 +1349,13 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
   constexpr bool HOLDS = persist_holds<R, FEXT, LOGIC, RESIDENT>();
   __shared__ HeldInputs held_lds[1];                 // (unreferenced, and not allocated, where !HOLDS)
   const bool hold = HOLDS && (a.epoch & AFE_PERSIST_HOLD);
+  // The engine word (reference noise streams) of a held chunk is held too, under the same condition -- while the grid lives
+  // only the grid writes it: every reader and writer of the slab on the host side ends the grid first (afe_engine.cpp
+  // persist_holds_inputs).  One lane-private dword per held chunk (HeldWords).  A tick then loads and stores
+  // no word (2 + 2 of the B per vehicle-step at a tick every other step), and its draws start without a round trip to
+  // memory; the words go back to the slab where the worker leaves the kernel (AFE_PUT_HELD_WORDS below).
+  constexpr bool WORD = RELOADS;
+  HeldWords words = {0, 0, 0};
   if (HOLDS && hold) {
     for (int j = 0, c = w; j < AFE_PERSIST_HELD_SLOTS && c < a.n_chunks; j++, c += a.n_workers) {
       const int64_t i = (int64_t)c * 64 + lane;
@@ -1338,9 +1364,26 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
         for (int m = 0; m < 4; m++) held_lds[0].v[j][m][lane] = v.cmd[m * v.stride + i];
 #pragma unroll
         for (int k = 0; k < 3; k++) held_lds[0].v[j][4 + k][lane] = (float)v.ext_force[k * v.stride + i];
+        if (WORD) {
+          words.put(j, v.rng[i]);
+        }
       }
     }
   }
+  // The held words go back to the slab before either way out of the one-step loops (the park entry, the give-up return).  The
+  // host collects a grid by waiting for the kernel's end (persist_collect), which makes these stores visible before anything
+  // reads the slab.  Through the kernel-argument segment like the loops below: nothing of the view stays alive for it.  (Spelt
+  // out at both returns: with one shared tail behind the poll loop the kernel is given a 36-byte private segment.)
+#define AFE_PUT_HELD_WORDS()                                                                                            \
+  do {                                                                                                                  \
+    if (WORD && hold) {                                                                                                 \
+      const PersistKernarg<R> &kw = persist_kernarg<R>();                                                               \
+      for (int j = 0, c = w; j < AFE_PERSIST_HELD_SLOTS && c < kw.a.n_chunks; j++, c += kw.a.n_workers) {               \
+        const int64_t i = (int64_t)c * 64 + lane;                                                                       \
+        if (i < kw.v.n) kw.v.rng[i] = words.get(j);                                                                     \
+      }                                                                                                                 \
+    }                                                                                                                   \
+  } while (0)
   // fewer chunks than the most loaded worker by a quarter or more: time to spare in every step
   const int mine = (a.n_chunks - w + a.n_workers - 1) / a.n_workers;   // this worker's chunks: w, w + W, ... (the one division)
   const bool spare = 4 * mine <= 3 * ((a.n_chunks + a.n_workers - 1) / a.n_workers);
@@ -1379,6 +1422,7 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
       if (waited > (u64_t)a.give_up_ticks + 1000000ull && lane == 0) st_agent(a.dev_ring - 1, 1);
       if (waited > (u64_t)a.give_up_ticks + 1050000000ull) {
         if (lane == 0) st_system(a.host_status + 2, 2);
+        AFE_PUT_HELD_WORDS();
         return;
       }
       // back off: a wave that has run into the ring's window (or waits for the host) must not hammer the memory system
@@ -1492,9 +1536,14 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
           c = w + j * ac.n_workers;
         } else if (c >= ac.n_chunks) break;
         const int64_t i = (int64_t)c * 64 + lane;
-        if (i < vc.n)
-          run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true, false, 0, HOLDS>(vc, RELOADS ? kc->P : P, RELOADS ? kc->G : G, i, tick, 1, tick_no,
-                                                                                 HOLDS ? &held_lds[0] : nullptr, hold && j < AFE_PERSIST_HELD_SLOTS ? j : -1);
+        if (i < vc.n) {
+          const int slot = hold && j < AFE_PERSIST_HELD_SLOTS ? j : -1;
+          // (the headline's call alone: nt on the IMU-sample stores and on the loads of inputs this worker does not hold --
+          // lines the grid never re-reads, kept from standing in the L2 among the state lines; the state stays default)
+          constexpr int GRID_CP = RELOADS ? 1 : 0;
+          run_vehicle<R, FEXT, false, NOISE, LOGIC, true, true, false, GRID_CP, HOLDS, WORD>(vc, RELOADS ? kc->P : P, RELOADS ? kc->G : G, i, tick, 1, tick_no,
+                                                                                             HOLDS ? &held_lds[0] : nullptr, slot, WORD ? &words : nullptr);
+        }
         if (!TURNS) c += ac.n_workers;
       }
       tick_no += tick;
@@ -1505,9 +1554,13 @@ afe_step_persistent_kernel(const StepView<R> v, const DevParams<R> P_arg, const 
       if (lane == 0 && a.n_workers <= AFE_PERSIST_HOST_MARKS) st_system(a.host_status + 8 + w, s);
     }
     if (lane == 0) st_agent(a.done + w, s);
-    if (parks) return;
+    if (parks) {
+      AFE_PUT_HELD_WORDS();
+      return;
+    }
     t_wait = ticks100();
   }
+#undef AFE_PUT_HELD_WORDS
 }
 
 // the same resampling for the launched kernels: one small launch when a step starts in a new epoch
