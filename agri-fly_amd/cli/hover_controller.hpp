@@ -78,8 +78,12 @@ struct HoverController {
     const Rotationf attNow(curAtt);
     const Vec3f correction = (Vec3f(refPos) - Vec3f(curPos)) * wn * wn + (Vec3f(refVel) - Vec3f(curVel)) * 2 * wn * zeta + Vec3f(0, 0, 0);
     outCmdThrust = refThrust + correction.Dot(attNow * up);
-    const Vec3f proper = Vec3f(refAcc) + correction + Vec3f(0, 0, 9.81f);
-    const Vec3f along = proper / proper.GetNorm2();
+    // refAcc is a Vec3d: the reference's sum widens the float correction and the float gravity and adds in DOUBLE (:99-101);
+    // the norm is narrowed to float, the division is double, and only its result becomes the float direction
+    // (tests/test_offboard_reference.py holds this line to the reference's own binary)
+    const Vec3d proper = refAcc + Vec3d(correction) + Vec3d(Vec3f(0, 0, 9.81f));
+    const float size = float(proper.GetNorm2());
+    const Vec3f along(proper / double(size));
     const float turn = AngleFromCosine(along.Dot(up), 1 - 1e-12f);
     const Vec3f axis = up.Cross(along);
     const float axisLen = axis.GetNorm2();

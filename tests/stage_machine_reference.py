@@ -5,9 +5,10 @@
   QuadcopterController::Run    Components/Components/Offboard/QuadcopterController.cpp:5-9, :11-74
                                (QuadcopterPositionController.hpp:22-28, QuadcopterAttitudeController.hpp:35-68, Rotation.hpp, Vec3.hpp)
 
-One vehicle, one object, one Run per period -- the shape of the reference, so that it can be read beside it.  The class
-needs ROS and Eigen headers and is compiled nowhere in this repository: this restatement is UNPINNED (nothing compares
-it with the reference's binary).  tests/stages_checker.py is the same arithmetic in numpy for N vehicles and must equal
+One vehicle, one object, one Run per period -- the shape of the reference, so that it can be read beside it.  SafetyNet and
+QuadcopterController::Run are PINNED: tests/test_offboard_reference.py holds them to what the reference's own code, compiled
+in place, computed (tests/golden/offboard_reference.npz).  ExampleVehicleStateMachine needs ROS headers and is compiled
+nowhere in this repository: the switch is UNPINNED (nothing compares it with the reference's binary).  tests/stages_checker.py is the same arithmetic in numpy for N vehicles and must equal
 this file bit for bit; agri-fly_amd/csrc/afe_stages.hip is the device's.
 
 Number formats: D = float64 where the reference says double, F = float32 where it says float; every narrowing is where

@@ -83,6 +83,26 @@ CONTROLLER_DRIVER = r'''
 #include "hover_controller.hpp"
 int main(int argc, char **argv) {
   agrifly_cli::HoverController ctrl;
+  if (argc > 1) {
+    // "run": records of 20 numbers (pos, vel, att, desired pos, vel, acc, yaw) -> Run; "track": records of 24 (pos, vel, att,
+    // reference pos, vel, acc, yaw, reference thrust, reference rates) -> RunTracking.  Hexadecimal floats in and out
+    // (tests/test_offboard_reference.py feeds the records of tests/golden/offboard_reference.npz).
+    const bool track = argv[1][0] == 't';
+    const int words = track ? 24 : 20;
+    double r[24];
+    for (;;) {
+      int got = 0;
+      for (int k = 0; k < words; k++) got += std::scanf("%lf", r + k) == 1;
+      if (got != words) break;
+      const Vec3d pos(r[0], r[1], r[2]), vel(r[3], r[4], r[5]), a(r[10], r[11], r[12]), b(r[13], r[14], r[15]), c(r[16], r[17], r[18]);
+      const Rotationd att(r[6], r[7], r[8], r[9]);
+      Vec3d w; double thr; Rotationf cmdAtt;
+      if (track) ctrl.RunTracking(pos, vel, att, a, b, c, r[19], r[20], Vec3d(r[21], r[22], r[23]), w, thr, cmdAtt);
+      else ctrl.Run(pos, vel, att, a, b, c, r[19], w, thr);
+      std::printf("%a %a %a %a\n", thr, w.x, w.y, w.z);
+    }
+    return 0;
+  }
   double in[10];
   while (std::scanf("%lf %lf %lf %lf %lf %lf %lf %lf %lf %lf", in, in + 1, in + 2, in + 3, in + 4, in + 5, in + 6, in + 7, in + 8, in + 9) == 10) {
     Vec3d w; double thr;
