@@ -1,6 +1,6 @@
 // afe_consumer.h -- host plumbing shared by the library's consumers of the engine's device state and by the perception
 // entry points: depth camera (afe_render.hip), planner API (afe_planner_api.cpp), clearance query, contact monitor and path
-// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip), mocap estimator (afe_estimator.hip), flight stage machine (afe_stages.hip).  Internal to the library, host only, header only.
+// audit (afe_clearance.hip), ensemble statistics (afe_stats.hip), trajectory follower (afe_follower.hip), mocap estimator (afe_estimator.hip), flight stage machine (afe_stages.hip), onboard flight computer (afe_onboard.hip).  Internal to the library, host only, header only.
 //
 //   engine_stream_device / engine_device_view / engine_shard   the engine's entry points for the library's other translation
 //                        units (implemented in afe_engine.cpp; afe_world.hip and afe_comm.cpp use the first and the last alone)
@@ -46,6 +46,27 @@ int engine_rates_slabs(afe_engine *e, float **rates_cmd, uint8_t **have_cmd);
 // caller has passed the gate and launches on the engine's stream.
 struct DevLogic;
 int engine_logic_filter(afe_engine *e, const float **lpf, const DevLogic **logic_table, float *period, uint64_t *n_ticks);
+// afe_engine.cpp: the clock of the latest logic tick for the onboard flight computer (afe_onboard.hip), which runs behind the step
+// that fired it.  *tick_start_us: the engine clock at the START of that step (the reference's logic reads the master clock inside
+// Quadcopter_T::Run, before main.cpp:392 advances it); *steps_after: steps issued since that step.  The caller has passed the gate.
+int engine_tick_clock(afe_engine *e, uint64_t *tick_start_us, uint64_t *steps_after);
+// THE RADIO MAILBOX: per-vehicle words of an onboard computer's handle (the engine's stride) that say which vehicles were handed
+// a radio message since its last tick: arrival time + 1 (0: none), RadioTypes type, flags.  The engine holds a BORROWED pointer
+// to them while an onboard computer exists (all NULL otherwise: then nothing changes for anybody).  Every place that delivers a
+// command stamps it: afe_set_rates_commands, afe_set_commands_from_radio, the follower's and the stage machine's tick.
+struct RadioMailbox {
+  unsigned long long *arrival;
+  uint8_t *type, *flags;
+};
+// afe_engine.cpp: records in the vehicle type table (a consumer's per-type table pairs with it)
+int engine_type_records(const afe_engine *e);
+// afe_engine.cpp: m == NULL withdraws; a second onboard computer on one engine is AFE_ERR_INVALID_ARG
+int engine_set_mailbox(afe_engine *e, const RadioMailbox *m);
+void engine_mailbox(const afe_engine *e, RadioMailbox *m);
+// afe_onboard.hip: stamp vehicles [first, first + count) on `stream`: arrival = now_us + 1; type >= 0: that type and flags 0 for
+// all; dev_types != NULL (a device row of the engine's stride, indexed by vehicle): each vehicle's own type, flags 0, and a
+// vehicle whose type is 0 was handed nothing and is left alone; type < 0 and no row: the arrival time alone.  m.arrival == NULL: nothing.
+int onboard_stamp(void *stream, const RadioMailbox &m, int64_t first, int64_t count, uint64_t now_us, int type, const uint8_t *dev_types);
 // afe_engine.cpp: AFE_ERR_INVALID_ARG for an engine whose state is host-visible (its setters go round the stream), for the
 // estimator, which like the follower works on the stream alone.  The caller has passed the gate.
 int engine_device_resident(afe_engine *e);

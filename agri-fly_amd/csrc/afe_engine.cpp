@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "afe_aql.h"
+#include "afe_consumer.h"
 #include "afe_host.h"
 #include "afe_render.h"
 #include "afe_world.h"
@@ -104,6 +105,10 @@ struct afe_engine {
   uint64_t now_us = 0;
   uint64_t logic_elapsed_us = 0;
   uint64_t n_ticks = 0;
+  // the latest tick, for the onboard flight computer (afe_onboard.hip): the clock at the START of the step that fired it -- the
+  // reference's logic reads the master clock inside Quadcopter_T::Run, before main.cpp:392 advances it -- and that step's ordinal
+  uint64_t tick_start_us = 0, tick_step = 0;
+  afe::RadioMailbox mailbox = {nullptr, nullptr, nullptr};   // borrowed from an onboard computer while one exists
   int max_fused = 64;
   int cache_policy = -1;       // afe_set_cache_policy: -1 automatic, 0..3 as LaunchFlags::cache_policy
   uint64_t steps_issued = 0;   // afe_steps_completed
@@ -1020,7 +1025,11 @@ int persist_step(afe_engine *e, uint64_t dt_us, int n_steps) {
     if (e->gust_on) e->gust_applied = e->now_us / e->gust_period_us;   // what the slab holds once this step has run
     e->now_us += dt_us;  // ManualTimer::AdvanceMicroSeconds, main.cpp:392
     unsigned long long entry = (e->p_next + 1) << 2;
-    if (gate_step(e->logic_period, e->logic_elapsed_us, dt_us)) { entry |= AFE_PERSIST_TICK; e->n_ticks++; }
+    if (gate_step(e->logic_period, e->logic_elapsed_us, dt_us)) {
+      entry |= AFE_PERSIST_TICK;
+      e->n_ticks++;
+      e->tick_start_us = e->now_us - dt_us; e->tick_step = e->steps_issued + 1;
+    }
     __atomic_store_n(&e->p_host[e->p_next & (AFE_PERSIST_HOST_RING - 1)], entry, __ATOMIC_RELEASE);
     e->p_next++;
     e->steps_issued++;
@@ -1381,6 +1390,19 @@ extern "C" int afe_set_rates_logic(afe_engine *e, const afe_rates_logic_params *
   return refresh_logic(e);
 }
 
+// SetRadioMessage's bookkeeping for an onboard computer (afe_consumer.h, THE RADIO MAILBOX): the arrival is stamped with the
+// clock as it stands now.  Without an onboard computer this is nothing.
+static int stamp_mailbox(afe_engine *e, int64_t first, int64_t count, int type, const uint8_t *types, const uint8_t *flags) {
+  if (!e->mailbox.arrival || count == 0) return AFE_OK;
+  int rc = main_stream(e);
+  if (rc) return rc;
+  if (onboard_stamp((void *)e->stream, e->mailbox, first, count, e->now_us, type, nullptr) != AFE_OK)
+    return fail(e, AFE_ERR_HIP, "radio mailbox stamp");
+  if (types && (rc = copy_in(e, e->mailbox.type, 1, 1, first, count, types))) return rc;
+  if (flags && (rc = copy_in(e, e->mailbox.flags, 1, 1, first, count, flags))) return rc;
+  return AFE_OK;
+}
+
 extern "C" int afe_set_rates_commands(afe_engine *e, int64_t first, int64_t count, const float *thrust_norm,
                                       const float *ang_vel3) {
   int rc = check_range(e, first, count);
@@ -1389,7 +1411,8 @@ extern "C" int afe_set_rates_commands(afe_engine *e, int64_t first, int64_t coun
   if (!thrust_norm || !ang_vel3) return fail(e, AFE_ERR_INVALID_ARG, "command arrays are NULL");
   if ((rc = copy_in(e, e->rates_cmd, 4, 1, first, count, thrust_norm))) return rc;
   if ((rc = copy_in(e, e->rates_cmd + e->stride, 4, 3, first, count, ang_vel3))) return rc;
-  return fill_rows(e, e->have_cmd, 1, 1, first, count, 1);
+  if ((rc = fill_rows(e, e->have_cmd, 1, 1, first, count, 1))) return rc;
+  return stamp_mailbox(e, first, count, 5, nullptr, nullptr);   // RadioTypes::externalRatesCmd
 }
 
 extern "C" int afe_get_rates_commands(afe_engine *e, int64_t first, int64_t count, float *thrust_norm, float *ang_vel3, uint8_t *have) {
@@ -1408,10 +1431,11 @@ extern "C" int afe_set_commands_from_radio(afe_engine *e, int64_t first, int64_t
   if (!e->logic_on) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_rates_logic has not been called");
   if (!raw_packets) return fail(e, AFE_ERR_INVALID_ARG, "raw_packets is NULL");
   std::vector<float> cmd((size_t)(4 * count));
-  std::vector<uint8_t> have((size_t)count);
+  std::vector<uint8_t> have((size_t)count), types((size_t)count), flags((size_t)count);
   for (int64_t k = 0; k < count; k++) {
     afe_radio_message m;
     afe_radio_decode(raw_packets + k * AFE_RADIO_PACKET_SIZE, &m);
+    types[(size_t)k] = m.type; flags[(size_t)k] = m.flags;
     if (m.type == 5) {  // externalRatesCmd -> FS_EXTERNAL_RATES_CONTROL (QuadcopterLogic.cpp:293-295)
       have[(size_t)k] = 1;
       for (int c = 0; c < 4; c++) cmd[(size_t)(c * count + k)] = m.floats[c];
@@ -1424,7 +1448,8 @@ extern "C" int afe_set_commands_from_radio(afe_engine *e, int64_t first, int64_t
     }
   }
   if ((rc = copy_in(e, e->rates_cmd, 4, 4, first, count, cmd.data()))) return rc;
-  return copy_in(e, e->have_cmd, 1, 1, first, count, have.data());
+  if ((rc = copy_in(e, e->have_cmd, 1, 1, first, count, have.data()))) return rc;
+  return stamp_mailbox(e, first, count, -1, types.data(), flags.data());
 }
 
 extern "C" int afe_set_external_force(afe_engine *e, int64_t first, int64_t count, const double *force3) {
@@ -1491,6 +1516,7 @@ extern "C" int afe_step(afe_engine *e, uint64_t dt_us, int n_steps) {
       if (gate_step(e->logic_period, e->logic_elapsed_us, dt_us)) {
         mask |= (1ull << s);
         e->n_ticks++;
+        e->tick_start_us = e->now_us - dt_us; e->tick_step = e->steps_issued + (uint64_t)s + 1;
       }
     }
     // launches without a logic tick draw no noise: use the lean instantiation
@@ -1728,6 +1754,20 @@ int engine_logic_filter(afe_engine *e, const float **lpf, const DevLogic **logic
   *n_ticks = e->n_ticks;
   return AFE_OK;
 }
+int engine_tick_clock(afe_engine *e, uint64_t *tick_start_us, uint64_t *steps_after) {
+  if (!e->logic_on) return fail(e, AFE_ERR_NOT_CONFIGURED, "afe_set_rates_logic has not been called");
+  *tick_start_us = e->tick_start_us;
+  *steps_after = e->steps_issued - e->tick_step;
+  return AFE_OK;
+}
+int engine_type_records(const afe_engine *e) { return (int)e->table.size(); }
+int engine_set_mailbox(afe_engine *e, const RadioMailbox *m) {
+  if (m && e->mailbox.arrival) return fail(e, AFE_ERR_INVALID_ARG, "the engine has an onboard computer already");
+  if (m) e->mailbox = *m;
+  else e->mailbox = RadioMailbox{nullptr, nullptr, nullptr};
+  return AFE_OK;
+}
+void engine_mailbox(const afe_engine *e, RadioMailbox *m) { *m = e->mailbox; }
 int engine_device_resident(afe_engine *e) {
   if (e->host_arena) return fail(e, AFE_ERR_INVALID_ARG, "the estimator needs an engine whose state is in device memory (afe_create)");
   return AFE_OK;
@@ -2015,6 +2055,9 @@ extern "C" int afe_load_checkpoint(afe_engine *e, const void *host_buffer, uint6
   e->now_us = h.now_us;
   e->logic_elapsed_us = h.logic_elapsed_us;
   e->n_ticks = h.n_ticks;
+  // the checkpoint does not carry the clock of the latest tick: an onboard computer is refused (a step counts as having run
+  // behind the tick) until the next tick fires
+  e->tick_start_us = 0; e->tick_step = ~0ull;
   e->has_ext_force = h.has_ext_force != 0;
   e->has_ext_torque = h.has_ext_torque != 0;
   e->noise = h.noise != 0;

@@ -800,6 +800,12 @@ extern "C" int afe_follower_tick(afe_follower *f, int64_t *n_tracking) {
         hipLaunchKernelGGL((afe_follower_tick_kernel<float, false>), grid, dim3(kBlock), 0, stream, g, (unsigned long long)now_us, write_slot, deliver_slot, announce);
     });
     if (rc != AFE_OK) return rc;
+    if (deliver_slot >= 0) {                                   // an onboard computer is told of the delivery (have_cmd = 1 above)
+      afe::RadioMailbox mail;
+      afe::engine_mailbox(f->engine, &mail);
+      rc = afe::onboard_stamp((void *)stream, mail, 0, g.n, now_us, 5, nullptr);
+      if (rc != AFE_OK) return rc;
+    }
   }
   if (f->est) afe::estimator_announce_commit(f->est, announce_from);
   for (size_t k = 0; k < n_due; k++) f->due.pop_front();

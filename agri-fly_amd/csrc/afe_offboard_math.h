@@ -16,6 +16,7 @@ __device__ __forceinline__ void fm_sincosf(float x, float *s, float *c) { *s = s
 __device__ __forceinline__ float fm_asinf(float x) { return asinf(x); }
 __device__ __forceinline__ float fm_acosf(float x) { return acosf(x); }
 __device__ __forceinline__ double fm_acos(double x) { return acos(x); }
+__device__ __forceinline__ float fm_atan2f(float y, float x) { return atan2f(y, x); }
 __device__ __forceinline__ void dm_sincos(double x, double *s, double *c) { *s = sin(x); *c = cos(x); }
 
 // ---- double ----------------------------------------------------------------------------------------------------------
@@ -149,6 +150,51 @@ __device__ __forceinline__ V3f qf_to_rotvec(const Q4f &q) {
 }
 __device__ __forceinline__ float tilt_angle(float c) {
   return c >= 1.0f ? 0.0f : c <= -1.0f ? 3.14159274f : fm_acosf(c);      // float(M_PI)
+}
+// `errno = 0; angle = acosf(c); if (errno) angle = c < 0 ? float(M_PI) : 0` (KalmanFilter6DOF.cpp:95-103, QuadcopterLogic.cpp:490-499):
+// glibc sets EDOM for |c| > 1 alone -- a NaN argument sets nothing and passes through
+__device__ __forceinline__ float guarded_acosf(float c) {
+  if (c > 1.0f) return 0.0f;
+  if (c < -1.0f) return 3.14159274f;                                       // float(M_PI)
+  return fm_acosf(c);
+}
+// Rotation::FromAxisAngle, Rotation.hpp:92-97 (a unit vector is the caller's business)
+__device__ __forceinline__ Q4f qf_from_axis_angle(const V3f &u, float angle) {
+#pragma clang fp contract(off)
+  float s, c;
+  fm_sincosf(angle * 0.5f, &s, &c);
+  Q4f q;
+  q.w = c; q.x = s * u.x; q.y = s * u.y; q.z = s * u.z;
+  return q;
+}
+// Rotation::FromEulerYPR, Rotation.hpp:99-110
+__device__ __forceinline__ Q4f qf_from_euler_ypr(float y, float p, float r) {
+#pragma clang fp contract(off)
+  float sy, cy, sp, cp, sr, cr;
+  fm_sincosf(0.5f * y, &sy, &cy);
+  fm_sincosf(0.5f * p, &sp, &cp);
+  fm_sincosf(0.5f * r, &sr, &cr);
+  Q4f q;
+  q.w = cy * cp * cr + sy * sp * sr;
+  q.x = cy * cp * sr - sy * sp * cr;
+  q.y = cy * sp * cr + sy * cp * sr;
+  q.z = sy * cp * cr - cy * sp * sr;
+  return q;
+}
+// Rotation::ToEulerYPR, Rotation.hpp:163-169
+__device__ __forceinline__ void qf_to_euler_ypr(const Q4f &q, float *y, float *p, float *r) {
+#pragma clang fp contract(off)
+  *y = fm_atan2f(2.0f * q.x * q.y + 2.0f * q.w * q.z, q.x * q.x + q.w * q.w - q.z * q.z - q.y * q.y);
+  *p = -fm_asinf(2.0f * q.x * q.z - 2.0f * q.w * q.y);
+  *r = fm_atan2f(2.0f * q.y * q.z + 2.0f * q.w * q.x, q.z * q.z - q.y * q.y - q.x * q.x + q.w * q.w);
+}
+// EncodeOnesRange(MapToOnesRange(x, a, b)), TelemetryPacket.hpp:38-60: outside [-1, 1] is code 0; the float sum is truncated to
+// 16 bits; a NaN (no comparison holds, the conversion is undefined in the reference) is code 0 here
+__device__ __forceinline__ uint16_t telemetry_code(float x, float a, float b) {
+#pragma clang fp contract(off)
+  const float t = ((x - a) / (b - a)) * 2 - 1;
+  if (t != t || t < -1 || t > 1) return 0;
+  return (uint16_t)(int)(32768 + 32767 * t);
 }
 // encodeToRadioByte + decodeFromRadioBytes, RadioTypes.hpp:73-116, two bytes, limit 35
 __device__ __forceinline__ float radio_quantise35(float v) {

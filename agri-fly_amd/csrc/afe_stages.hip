@@ -662,6 +662,12 @@ extern "C" int afe_stages_tick(afe_stages *s, int should_start, int should_stop,
       hipLaunchKernelGGL((afe_stages_tick_kernel<float, false>), grid, dim3(kBlock), 0, stream, g, now, est_now, start, stop, write_slot, deliver_slot);
   });
   if (rc != AFE_OK) return rc;
+  if (deliver_slot >= 0) {                                       // an onboard computer is told of the delivery (have_cmd above):
+    afe::RadioMailbox mail;                                      // each vehicle's delivered type, type 0 was handed nothing
+    afe::engine_mailbox(s->engine, &mail);
+    rc = afe::onboard_stamp((void *)stream, mail, 0, g.n, now_us, -1, g.ring_type + (int64_t)deliver_slot * g.stride);
+    if (rc != AFE_OK) return rc;
+  }
   for (size_t k = 0; k < n_due; k++) s->due.pop_front();
   if (!own_due) s->due.push_back(now_us + s->delay_us);
   s->seq++;

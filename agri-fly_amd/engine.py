@@ -77,6 +77,9 @@ ABI_FUNCTIONS = [
     "afe_stages_default_config", "afe_stages_create", "afe_stages_destroy", "afe_stages_info", "afe_stages_set_desired_position",
     "afe_stages_set_desired_yaw", "afe_stages_set_centre", "afe_stages_set_unsafe", "afe_stages_request", "afe_stages_set_warnings",
     "afe_stages_tick", "afe_stages_get", "afe_stages_attach_gps_estimator", "afe_stages_selftest_math",
+    "afe_onboard_default_config", "afe_onboard_create", "afe_onboard_destroy", "afe_onboard_info", "afe_onboard_set_battery",
+    "afe_onboard_radio", "afe_onboard_tick", "afe_onboard_get", "afe_onboard_set_state", "afe_onboard_telemetry",
+    "afe_onboard_selftest_math",
 ]
 
 
@@ -215,6 +218,34 @@ class StagesFields(C.Structure):
                 ("computed4", C.c_void_p), ("sent4", C.c_void_p), ("msg_type", C.c_void_p)]
 
 
+class OnboardConfig(C.Structure):
+    """afe_onboard_config (onboard_default_config sets struct_bytes)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("accel_lowpass_cutoff", C.c_float), ("batt_lowpass_cutoff", C.c_float),
+                ("temp_lowpass_cutoff", C.c_float), ("main_loop_monitor_cutoff", C.c_float), ("cmd_rate_monitor_cutoff", C.c_float),
+                ("att_time_const_xy", C.c_float), ("att_time_const_z", C.c_float), ("low_battery_threshold", C.c_float),
+                ("radio_cmd_period", C.c_float)]
+
+
+class OnboardFields(C.Structure):
+    """afe_onboard_fields: where afe_onboard_get writes (NULL: not read back)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("flight_state", C.c_void_p), ("panic_reason", C.c_void_p), ("warnings", C.c_void_p),
+                ("est_att4", C.c_void_p), ("est_ang_vel3", C.c_void_p), ("acc_filtered3", C.c_void_p), ("batt_filtered", C.c_void_p),
+                ("main_loop_dt", C.c_void_p), ("cmd_dt", C.c_void_p), ("motor_forces4", C.c_void_p), ("cycle_counter", C.c_void_p),
+                ("last_radio_us", C.c_void_p), ("motors_running", C.c_void_p)]
+
+
+class OnboardState(C.Structure):
+    """afe_onboard_state: what afe_onboard_set_state writes (NULL: left as it is)"""
+    _fields_ = [("struct_bytes", C.c_size_t), ("est_att4", C.c_void_p), ("est_ang_vel3", C.c_void_p), ("imu_initialized", C.c_void_p),
+                ("lowpass20", C.c_void_p), ("flight_state", C.c_void_p), ("motors_running", C.c_void_p), ("last_radio_us", C.c_void_p)]
+
+
+AFE_FS_UNINITIALIZED, AFE_FS_IDLE, AFE_FS_FULLY_AUTONOMOUS, AFE_FS_PANIC, AFE_FS_KILLED, AFE_FS_EXTERNAL_ACCELERATION_CONTROL, \
+    AFE_FS_EXTERNAL_RATES_CONTROL = range(7)
+AFE_PANIC_NO_PANIC, AFE_PANIC_ONBOARD_ESTIMATE_CRAZY, AFE_PANIC_UWB_TIMEOUT, AFE_PANIC_UPSIDE_DOWN, AFE_PANIC_RADIO_CMD_TIMEOUT, \
+    AFE_PANIC_LOW_BATTERY, AFE_PANIC_KILLED_INTERNALLY, AFE_PANIC_KILLED_EXTERNALLY = range(8)
+AFE_WARN_CMD_RATE, AFE_WARN_UWB_RESET, AFE_WARN_ONBOARD_FREQ, AFE_WARN_CMD_BATCH_DROP = 0x02, 0x04, 0x08, 0x10
+AFE_RADIO_FLAG_DISABLE_SAFETY_CHECKS = 0x02
 AFE_STAGE_WAIT_FOR_START, AFE_STAGE_SPOOL_UP, AFE_STAGE_TAKEOFF, AFE_STAGE_FLIGHT, AFE_STAGE_LANDING, AFE_STAGE_COMPLETE, \
     AFE_STAGE_EMERGENCY = range(7)
 AFE_SAFETY_NOT_SEEN, AFE_SAFETY_UNSAFE_POSITION, AFE_SAFETY_UPSIDE_DOWN_AND_LOW, AFE_SAFETY_USER_UNSAFE = 1, 2, 4, 8
@@ -537,6 +568,17 @@ def library():
         "afe_stages_get": [vp, i64, i64, C.POINTER(StagesFields)],
         "afe_stages_attach_gps_estimator": [vp, vp],
         "afe_stages_selftest_math": [ci, ci, i64, vp, vp],
+        "afe_onboard_default_config": [ci, C.POINTER(OnboardConfig)],
+        "afe_onboard_create": [eng, C.POINTER(OnboardConfig), ci, C.POINTER(vp)],
+        "afe_onboard_destroy": [vp],
+        "afe_onboard_info": [vp, C.POINTER(i64), C.POINTER(u64), C.POINTER(u64)],
+        "afe_onboard_set_battery": [vp, i64, i64, vp],
+        "afe_onboard_radio": [vp, i64, i64, vp],
+        "afe_onboard_tick": [vp, vp],
+        "afe_onboard_get": [vp, i64, i64, C.POINTER(OnboardFields)],
+        "afe_onboard_set_state": [vp, i64, i64, C.POINTER(OnboardState)],
+        "afe_onboard_telemetry": [vp, i64, i64, vp],
+        "afe_onboard_selftest_math": [ci, ci, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -588,6 +630,24 @@ def radio_create_rates_command(flags, thrust, ang_vel):
     rc = library().afe_radio_create_rates_command(int(flags), float(thrust), w.ctypes.data, raw.ctypes.data)
     if rc:
         raise AfeError(rc, "afe_radio_create_rates_command")
+    return raw
+
+
+def radio_create_acceleration_command(flags, acc, yaw_rate):
+    raw = np.zeros(RADIO_PACKET_SIZE, np.uint8)
+    a = np.ascontiguousarray(acc, dtype=np.float32)
+    rc = library().afe_radio_create_acceleration_command(int(flags), a.ctypes.data, float(yaw_rate), raw.ctypes.data)
+    if rc:
+        raise AfeError(rc, "afe_radio_create_acceleration_command")
+    return raw
+
+
+def radio_create_simple_command(msg_type, flags=0):
+    """kill (2) or idle (6)"""
+    raw = np.zeros(RADIO_PACKET_SIZE, np.uint8)
+    rc = library().afe_radio_create_simple_command(int(msg_type), int(flags), raw.ctypes.data)
+    if rc:
+        raise AfeError(rc, "afe_radio_create_simple_command")
     return raw
 
 
@@ -1660,6 +1720,139 @@ class FlightStages:
             self._h = C.c_void_p()
             self._keep = None
             self._gps = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def onboard_default_config(quadcopter_type):
+    """afe_onboard_default_config: QuadcopterLogic::Initialise's cut-offs, the attitude controller's time constants, the battery
+    threshold and the radio period for the type.  Pure host."""
+    c = OnboardConfig()
+    _status(library().afe_onboard_default_config(int(quadcopter_type), C.byref(c)))
+    return c
+
+
+ONBOARD_MATH_OPS = {"sinf": 0, "cosf": 1, "acosf": 2, "asinf": 3, "atan2f": 4}
+
+
+def onboard_selftest_math(op, x, x2=None, device=-1):
+    """afe_onboard_selftest_math: the device library's sinf / cosf / acosf / asinf of x, or atan2f(x, x2), as the onboard
+    computer's kernel calls them; op is a name or 0..4"""
+    op = ONBOARD_MATH_OPS.get(op, op)
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(a)
+    if op == 4:
+        arg = np.ascontiguousarray(np.stack([a.ravel(), np.ascontiguousarray(x2, dtype=np.float32).ravel()]))
+    else:
+        arg = a
+    _status(library().afe_onboard_selftest_math(int(device), int(op), a.size, arg.ctypes.data, y.ctypes.data))
+    return y
+
+
+class Onboard:
+    """afe_onboard: the vehicle's own flight computer -- attitude estimate, radio parsing with sticky PANIC / KILLED, telemetry
+    warnings, panic checks, the external-acceleration controller and the telemetry packets -- for every vehicle of an ensemble,
+    on the device (see the header).  cfgs: one OnboardConfig per type record (default: quadcopter_type's for every record).
+    Borrows the ensemble: close the onboard computer first."""
+
+    _FIELDS = (("flight_state", np.uint8, 0), ("panic_reason", np.uint8, 0), ("warnings", np.uint8, 0), ("est_att", np.float32, 4),
+               ("est_ang_vel", np.float32, 3), ("acc_filtered", np.float32, 3), ("batt_filtered", np.float32, 0),
+               ("main_loop_dt", np.float32, 0), ("cmd_dt", np.float32, 0), ("motor_forces", np.float32, 4),
+               ("cycle_counter", np.uint32, 0), ("last_radio_us", np.uint64, 0), ("motors_running", np.uint8, 0))
+    _STATE = (("est_att4", np.float32, 4), ("est_ang_vel3", np.float32, 3), ("imu_initialized", np.uint8, 0), ("lowpass20", np.float32, 20),
+              ("flight_state", np.uint8, 0), ("motors_running", np.uint8, 0), ("last_radio_us", np.uint64, 0))
+
+    def __init__(self, ensemble, cfgs=None, quadcopter_type=5, n_types=1):
+        if cfgs is None:
+            cfgs = [onboard_default_config(quadcopter_type) for _ in range(n_types)]
+        self.cfgs = list(cfgs)
+        table = (OnboardConfig * len(self.cfgs))(*self.cfgs)
+        self._h = C.c_void_p()
+        self.n = ensemble.n
+        self._keep = ensemble
+        _status(library().afe_onboard_create(ensemble.handle, table, len(self.cfgs), C.byref(self._h)))
+
+    def _range(self, first, count):
+        first = int(first)
+        return first, int(self.n - first if count is None else count)
+
+    def set_battery(self, volts, first=0):
+        a = np.ascontiguousarray(volts, dtype=np.float32)
+        assert a.ndim == 1
+        _status(library().afe_onboard_set_battery(self._h, int(first), a.size, a.ctypes.data))
+
+    def radio(self, raw_packets, first=0):
+        """SetCommandRadioMsg: raw_packets uint8 [count, RADIO_PACKET_SIZE]; types 2, 4, 5, 6"""
+        a = np.ascontiguousarray(raw_packets, dtype=np.uint8)
+        assert a.ndim == 2 and a.shape[1] == RADIO_PACKET_SIZE
+        _status(library().afe_onboard_radio(self._h, int(first), a.shape[0], a.ctypes.data))
+
+    def tick(self, count=False):
+        """one Run() behind the step that fired the logic tick; -> int64 [16]: vehicles per flight state [0..6], per first panic
+        reason [7..14], with any warning [15] (count), or None (then nothing is downloaded and the call does not wait)"""
+        if not count:
+            _status(library().afe_onboard_tick(self._h, None))
+            return None
+        c = np.zeros(16, np.int64)
+        _status(library().afe_onboard_tick(self._h, c.ctypes.data))
+        return c
+
+    def get(self, first=0, count=None, fields=None):
+        """-> dict of the computer's per-vehicle state (all of _FIELDS, or those named), planar [comps, count]"""
+        first, count = self._range(first, count)
+        names = [f[0] for f in self._FIELDS] if fields is None else list(fields)
+        out, req = {}, OnboardFields()
+        req.struct_bytes = C.sizeof(OnboardFields)
+        for name, dtype, comps in self._FIELDS:
+            if name in names:
+                out[name] = np.empty((comps, count) if comps else (count,), dtype)
+                setattr(req, name + (str(comps) if comps else ""), out[name].ctypes.data)
+        if len(out) != len(names):
+            raise ValueError("unknown fields %r" % sorted(set(names) - set(out)))
+        _status(library().afe_onboard_get(self._h, first, count, C.byref(req)))
+        return out
+
+    def set_state(self, first=0, **fields):
+        """afe_onboard_set_state: est_att4, est_ang_vel3, imu_initialized, lowpass20, flight_state, motors_running, last_radio_us;
+        planar [comps, count], what is not named is left as it is"""
+        req, keep, count = OnboardState(), [], None
+        req.struct_bytes = C.sizeof(OnboardState)
+        for name, dtype, comps in self._STATE:
+            if name in fields:
+                a = np.ascontiguousarray(fields.pop(name), dtype=dtype)
+                assert a.shape[:-1] == ((comps,) if comps else ()) and count in (None, a.shape[-1])
+                count = a.shape[-1]
+                keep.append(a)
+                setattr(req, name, a.ctypes.data)
+        if fields:
+            raise ValueError("unknown fields %r" % sorted(fields))
+        _status(library().afe_onboard_set_state(self._h, int(first), int(count or 0), C.byref(req)))
+
+    def telemetry(self, first=0, count=None):
+        """GetTelemetryDataPackets -> uint8 [count, 2, TELEMETRY_PACKET_SIZE]; the range's packet counters advance and its
+        warnings are cleared"""
+        first, count = self._range(first, count)
+        out = np.zeros((count, 2, TELEMETRY_PACKET_SIZE), np.uint8)
+        _status(library().afe_onboard_telemetry(self._h, first, count, out.ctypes.data))
+        return out
+
+    def info(self):
+        nv, nt, lt = C.c_int64(), C.c_uint64(), C.c_uint64()
+        _status(library().afe_onboard_info(self._h, C.byref(nv), C.byref(nt), C.byref(lt)))
+        return {"n_vehicles": nv.value, "n_ticks": nt.value, "last_tick": lt.value}
+
+    def close(self):
+        """afe_onboard_destroy withdraws the mailbox from the engine: if the ensemble was closed first (the wrong order) the
+        engine is gone and the handle is dropped without the call (its device memory went with the engine's context)"""
+        if getattr(self, "_h", None):
+            if self._keep is not None and getattr(self._keep, "_h", None):
+                library().afe_onboard_destroy(self._h)
+            self._h = C.c_void_p()
+            self._keep = None
 
     def __del__(self):
         try:

@@ -257,9 +257,10 @@ int afe_set_external_torque(afe_engine *e, int64_t first, int64_t count, const d
  *       QuadcopterMixer::GetMotorForces / PropellerSpeedsFromThrust
  *       (QuadcopterMixer.hpp:63-99)
  * and write the four motor-speed commands, which act from the next step on as
- * in Quadcopter_T.cpp:187-189.  Not included: the flight-state machine beyond
- * IDLE -> EXTERNAL_RATES_CONTROL, panic checks, attitude estimate, telemetry,
- * motor calibration (host-side logic).  All logic arithmetic is float, as in
+ * in Quadcopter_T.cpp:187-189.  Not included here: the flight-state machine beyond
+ * IDLE -> EXTERNAL_RATES_CONTROL, panic checks, attitude estimate, telemetry (the onboard
+ * flight computer below, afe_onboard_*, adds them behind the tick), motor calibration
+ * (host-side logic).  All logic arithmetic is float, as in
  * the reference.  Record i of the logic table pairs with record i of the
  * vehicle type table. */
 typedef struct afe_rates_logic_params {
@@ -1122,7 +1123,9 @@ int afe_follower_attach_gps_estimator(afe_follower *f, afe_gps_estimator *g);
  * tests/stages_checker.py in numpy.  The class needs ROS and Eigen headers and is compiled nowhere here: the restatement is NOT
  * pinned to the reference's binary.
  * Two writers: a follower and a stage machine on one engine both write the rates command; the last writer's stands.
- * The on-device logic has no sticky FS_KILLED: Emergency is never left and sends a kill every period, so the effect is the same.
+ * The step kernel's logic has no sticky FS_KILLED: Emergency is never left and sends a kill every period, so the effect is the same
+ * (with an onboard flight computer, afe_onboard_*, FS_KILLED and FS_PANIC are sticky, and afe_onboard_telemetry is a source for
+ * afe_stages_set_warnings).
  * Not covered: the mocap node's variant of the class (the device mocap estimator keeps no last-good-measurement time and its
  * announce ring needs per-stage rules), PublishEstimate's Euler angles, delivery between ticks, rappids_headless.
  * Indices are engine-local.  The machine BORROWS the engine (and an attached estimator) and needs an engine whose state is in
@@ -1205,6 +1208,120 @@ int afe_stages_attach_gps_estimator(afe_stages *s, afe_gps_estimator *g);
 /* Self-test hook: the device library's functions exactly as the tick kernel calls them, through the same helpers, on GPU
  * `device` (< 0: current).  op 0, 1 = sin, cos (x, y double [n]); op 2..5 = sinf, cosf, asinf, acosf (x, y float [n]). */
 int afe_stages_selftest_math(int device, int op, int64_t n, const void *x, void *y);
+
+/* ---- onboard flight computer (csrc/afe_onboard.hip) -----------------------------------------------------------------------
+ * The rest of Onboard::QuadcopterLogic::Run (Components/Components/Logic/QuadcopterLogic.cpp:164-219 with what
+ * Quadcopter_T.cpp:163-185 hands it) for a whole ensemble WITHOUT UWB ranging: battery, accelerometer and temperature low-passes,
+ * the main-loop and command-rate monitors, the attitude estimate of KalmanFilter6DOF::Predict's complementary branch
+ * (KalmanFilter6DOF.cpp:70-147 -- all the reference executes when no UWB network exists, and Rappids_Simulator builds none),
+ * ParseIncomingCommunications with STICKY FS_PANIC and FS_KILLED, the five telemetry warnings, CheckPanicReasons, the
+ * external-acceleration controller and the telemetry packets.  A consumer of the engine like the follower and the stage
+ * machine: one lane per vehicle, planar slabs of its own, the engine's stream, one kernel per logic tick BEHIND the step that
+ * fired the tick; no step kernel knows about it.  The step kernel keeps computing the rates command (one writer per value):
+ * for a vehicle in FS_EXTERNAL_RATES_CONTROL the onboard tick leaves the command as it stands, in the acceleration state it
+ * writes its own four motor speeds, and in IDLE, PANIC and KILLED it writes zeros OVER what the step kernel wrote.
+ * csrc/afe_onboard.hip states every value operation by operation; tests/onboard_checker.py restates it in numpy.  The
+ * restatement is unpinned except for the parts listed in the README (QuadcopterLogic.hpp pulls in the 9x9 Eigen filter).
+ * THE CLOCK of a tick is the engine clock at the START of the step that fired it (the reference's logic reads the master clock
+ * inside Quadcopter_T::Run, before main.cpp:392 advances it).  Radio arrivals carry afe_time_us at the moment of delivery.
+ * THE RADIO MAILBOX: while an onboard computer exists every delivery of a command -- afe_set_rates_commands (type 5, flags 0),
+ * afe_set_commands_from_radio, a follower's or stage machine's tick, afe_onboard_radio -- also records (arrival time, type,
+ * flags) per vehicle.  ONE delivery per vehicle between two onboard ticks is represented: a second one overwrites the first
+ * and the command-rate monitor sees one.  A delivery stamped later than the tick's clock (made between the ticking step and the
+ * onboard tick) waits for the next tick -- but its floats are in the rates-command slab already, so for that one tick the
+ * telemetry forces of a rates-state vehicle come from the new command and its motor command from the old one: deliver between
+ * ticks.  After afe_load_checkpoint the clock of the latest tick is unknown: afe_onboard_tick is refused until the next tick has fired.
+ * Without an onboard computer nothing changes for anybody.
+ * NOT BUILT: UWB range updates and the 9x9 covariance, FS_FULLY_AUTONOMOUS (a position command is refused), TestMotors, gyro
+ * and propeller calibration (a calibrateMotors flag is ignored).  Estimated position and velocity stay 0, as in the reference
+ * without UWB, so PANIC_ONBOARD_ESTIMATE_CRAZY and PANIC_UWB_TIMEOUT cannot fire; both comparisons are kept in the code.
+ * It equals the reference's vehicle only when created before the first logic tick (its filters and timers start at creation).
+ * Indices are engine-local.  The computer BORROWS the engine; destroy order: onboard computer, then the engine. */
+enum {                                    /* QuadcopterLogic::FlightState, QuadcopterLogic.hpp:148-157 */
+  AFE_FS_UNINITIALIZED = 0, AFE_FS_IDLE = 1, AFE_FS_FULLY_AUTONOMOUS = 2, AFE_FS_PANIC = 3, AFE_FS_KILLED = 4,
+  AFE_FS_EXTERNAL_ACCELERATION_CONTROL = 5, AFE_FS_EXTERNAL_RATES_CONTROL = 6, AFE_FS_COUNT = 7
+};
+enum {                                    /* PanicReason.hpp */
+  AFE_PANIC_NO_PANIC = 0, AFE_PANIC_ONBOARD_ESTIMATE_CRAZY = 1, AFE_PANIC_UWB_TIMEOUT = 2, AFE_PANIC_UPSIDE_DOWN = 3,
+  AFE_PANIC_RADIO_CMD_TIMEOUT = 4, AFE_PANIC_LOW_BATTERY = 5, AFE_PANIC_KILLED_INTERNALLY = 6, AFE_PANIC_KILLED_EXTERNALLY = 7,
+  AFE_PANIC_COUNT = 8
+};
+#define AFE_WARN_CMD_RATE 0x02            /* TelemetryPacket.hpp:22-27 */
+#define AFE_WARN_UWB_RESET 0x04
+#define AFE_WARN_ONBOARD_FREQ 0x08
+#define AFE_WARN_CMD_BATCH_DROP 0x10
+#define AFE_RADIO_FLAG_DISABLE_SAFETY_CHECKS 0x02   /* RadioTypes::disableOnboardStateSafetyChecks */
+typedef struct afe_onboard afe_onboard;
+typedef struct afe_onboard_config {
+  size_t struct_bytes;          /* IN: sizeof(afe_onboard_config) as the caller was compiled; less is AFE_ERR_INVALID_ARG */
+  float accel_lowpass_cutoff;   /* [rad/s] 100                  QuadcopterLogic.cpp:102 */
+  float batt_lowpass_cutoff;    /* [rad/s] 0.5f * float(2 pi)   :104 */
+  float temp_lowpass_cutoff;    /* [rad/s] 0.5f * float(2 pi)   :105 */
+  float main_loop_monitor_cutoff; /* [rad/s] 50                 :15 */
+  float cmd_rate_monitor_cutoff;  /* [rad/s] 1                  :14 */
+  float att_time_const_xy, att_time_const_z;   /* QuadcopterConstants attControl_timeConst_* */
+  float low_battery_threshold;  /* [V] afe_low_battery_threshold_from_type; the warning is at 1.05f x this */
+  float radio_cmd_period;       /* [s] 0.02                     :10 */
+} afe_onboard_config;
+/* The reference's values for the type (1, 2, 4, 5; else AFE_ERR_INVALID_ARG).  Pure host. */
+int afe_onboard_default_config(int quadcopter_type, afe_onboard_config *cfg);
+/* Initialise() for every vehicle: FS_IDLE, no panic, filters at their initial values, battery measurement 1.2f x threshold of the
+ * vehicle's type, all timers reset to afe_time_us.  cfg_table: one config per type record (n_types must equal the type table's
+ * size; it pairs with the logic table).  AFE_ERR_NOT_CONFIGURED without afe_set_rates_logic, AFE_ERR_INVALID_ARG for a
+ * host-visible engine or an engine that has an onboard computer already. */
+int afe_onboard_create(afe_engine *e, const afe_onboard_config *cfg_table, int n_types, afe_onboard **out);
+int afe_onboard_destroy(afe_onboard *o);   /* withdraws the mailbox from the engine; NULL is AFE_ERR_INVALID_ARG */
+/* (any output may be NULL) onboard ticks so far; the afe_logic_ticks value the last one consumed (0: none) */
+int afe_onboard_info(const afe_onboard *o, int64_t *n_vehicles, uint64_t *n_ticks, uint64_t *last_tick);
+/* The voltage Quadcopter_T hands SetBatteryMeasurement at every tick, volts [count].  NULL is AFE_ERR_INVALID_ARG; count == 0
+ * with a valid range is AFE_OK without touching the engine. */
+int afe_onboard_set_battery(afe_onboard *o, int64_t first, int64_t count, const float *volts);
+/* SetCommandRadioMsg for a vehicle with an onboard computer, raw_packets [count][AFE_RADIO_PACKET_SIZE].  Types 2, 5, 6 do what
+ * afe_set_commands_from_radio does; type 4 (externalAccelerationCmd) stores its four floats for the onboard controller and
+ * clears the vehicle's rates command; any other type (3, the position command, needs the range filter) is
+ * AFE_ERR_INVALID_ARG with nothing applied. */
+int afe_onboard_radio(afe_onboard *o, int64_t first, int64_t count, const uint8_t *raw_packets);
+/* One Run() for every vehicle with the IMU sample of the latest logic tick.  AFE_ERR_NOT_CONFIGURED, with nothing changed, unless
+ * afe_logic_ticks is exactly one more than at the previous call (the first call: one more than at creation) and no step has run
+ * after the ticking one (afe_steps_until_tick says how far to step).  counts16 (may be NULL: then nothing is
+ * downloaded and the call does not wait): vehicles per flight state after the tick [0..6], per first panic reason [7..14], and
+ * vehicles with any warning bit accumulated [15]. */
+int afe_onboard_tick(afe_onboard *o, int64_t *counts16);
+/* What afe_onboard_get reads back, planar [comps][count]; a pointer that is NULL is not read back, all NULL is AFE_ERR_INVALID_ARG. */
+typedef struct afe_onboard_fields {
+  size_t struct_bytes;          /* IN: sizeof(afe_onboard_fields) */
+  uint8_t *flight_state;        /* AFE_FS_* */
+  uint8_t *panic_reason;        /* _firstPanicReason, AFE_PANIC_* */
+  uint8_t *warnings;            /* _telWarnings: accumulated since the last telemetry */
+  float *est_att4, *est_ang_vel3;   /* GetEstimate (position and velocity are 0) */
+  float *acc_filtered3;         /* _imuAccelerometer.lowPass.GetValue() */
+  float *batt_filtered;         /* _battMeas.voltageFiltered */
+  float *main_loop_dt, *cmd_dt; /* the two MonitorSimplePeriod::lpDt */
+  float *motor_forces4;         /* _desMotorForcesForTelemetry */
+  uint32_t *cycle_counter;
+  uint64_t *last_radio_us;      /* afe_time_us at the last SetRadioMessage (creation time: none yet) */
+  uint8_t *motors_running;      /* GetAreMotorsRunning() after the last tick */
+} afe_onboard_fields;
+int afe_onboard_get(afe_onboard *o, int64_t first, int64_t count, const afe_onboard_fields *fields);
+/* For tests and resumption, planar [comps][count]; NULL leaves a field as it is, all NULL is AFE_ERR_INVALID_ARG.  lowpass20:
+ * xm0, xm1, ym0, ym1 of the accelerometer (3 each, 12 rows), then of the battery (4 rows) and the temperature (4 rows). */
+typedef struct afe_onboard_state {
+  size_t struct_bytes;          /* IN: sizeof(afe_onboard_state) */
+  const float *est_att4, *est_ang_vel3;
+  const uint8_t *imu_initialized;   /* KalmanFilter6DOF::_IMUInitialized: 0 makes the next tick rebuild the attitude */
+  const float *lowpass20;
+  const uint8_t *flight_state;
+  const uint8_t *motors_running;
+  const uint64_t *last_radio_us;
+} afe_onboard_state;
+int afe_onboard_set_state(afe_onboard *o, int64_t first, int64_t count, const afe_onboard_state *state);
+/* GetTelemetryDataPackets (QuadcopterLogic.cpp:621-679): packets [count][2][AFE_TELEMETRY_PACKET_SIZE], both parts per vehicle
+ * (bytes the reference leaves unwritten are 0).  Afterwards the packet counter of the vehicles IN THE RANGE is incremented and
+ * their warnings are cleared. */
+int afe_onboard_telemetry(afe_onboard *o, int64_t first, int64_t count, uint8_t *packets);
+/* Self-test hook: the device library's functions exactly as the tick kernel calls them, through the same helpers, on GPU
+ * `device` (< 0: current).  op 0..3 = sinf, cosf, acosf, asinf (x, y float [n]); op 4 = atan2f (x float [2][n]: y then x). */
+int afe_onboard_selftest_math(int device, int op, int64_t n, const float *x, float *y);
 
 /* ---- stepping -----------------------------------------------------------
  * afe_step replaces the loop body
