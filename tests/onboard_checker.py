@@ -10,7 +10,13 @@ the same; agri-fly_amd/csrc/afe_onboard.hip states the same operations for the d
 PINNED PARTS: the second-order low-pass is tests/gps_imu_reference.py's (held to the oracle library's ora_lpf2_* in
 tests/test_onboard_cpu.py), the quaternion functions are tests/follower_checker.py's and the attitude controller is
 tests/stages_checker.desired_angular_velocity (both pinned through tests/golden/offboard_reference.npz); the command of the rates
-state is held to ora_logic_tick and the telemetry bytes to afe_telemetry_encode.  Everything else is an UNPINNED restatement."""
+state is held to ora_logic_tick and the telemetry bytes to afe_telemetry_encode.
+
+PINNED AS A WHOLE to the reference's own class: oracle/_ref/onboard_probe (QuadcopterLogic.cpp and KalmanFilter6DOF.cpp compiled
+where they lie against oracle/eigen_trap) flies the script of tests/onboard_flight.py call for call, and under glibc_math every
+field of every vehicle after every tick and every telemetry byte of this file equals it bit for bit
+(tests/golden/make_onboard_reference.py asserts it, tests/test_onboard_reference.py holds this file to the recording).  Still
+open: the branch behind _UWBInitialized, RunControllerFullyAutonomous, TestMotors, the calibrations (none is stated here)."""
 import ctypes as _C
 import ctypes.util as _Cu
 

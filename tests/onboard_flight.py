@@ -9,6 +9,7 @@
   fly_beside(afa, e, ob, ticks, ...)     the loop beside a live sender: a stage machine's or a follower's tick every few ticks
   replay(afa, record, math)              the same script through tests/onboard_checker.py on the recorded samples
   replay_scalar(afa, record, math)       ... and through tests/onboard_reference.py, one vehicle at a time
+  drive_scalar(afa, record, make)        the driver under replay_scalar, for any object with the scalar Vehicle's five methods
   synthetic_record(afa)                  a record without a device, for the CPU tests
 
 Events of the script:
@@ -33,7 +34,30 @@ PERIOD = 1.0 / 500.0
 SILENCE_FROM = 30            # the tick after which the silent range hears nothing any more
 SLOW_FROM, SLOW_TO = 300, 320
 OVERRIDE_AT = 765            # (T is past 1.5 s there: a radio timer set back to 0 has run out)
+EDGE_AT = 752                # the last silent vehicle's radio timer stands at EXACTLY 1 500 000 us at this tick: no time-out yet (placed at 750)
+NAN_FIRST = 37               # synthetic_record alone: this plain vehicle's FIRST accelerometer sample is NaN (acosf of a NaN cosine)
 TICKS = 1200                 # 2.4 s: the radio time-out (1.5 s after the last message at tick SILENCE_FROM) falls at two thirds
+
+
+def tick_clocks(ticks=TICKS):
+    """(now, T, after) of every tick under the loop of fly_device -- step until the vehicle's tick gate fires (Quadcopter_T.cpp:159-160,
+    tests/onboard_reference.TickGate: more than a period since the gate's timer, which then moves on by ONE period); T is the clock
+    at the start of the ticking step.  1 ms steps under the 2 ms period: the first tick fires on the third step, then on every
+    second; 3 ms steps fire one each and leave the gate 1 ms further behind every time, so that after the slow stretch every 1 ms
+    step fires a tick until the backlog is gone"""
+    from tests import onboard_reference as orf
+    clock = orf.Clock(0)
+    gate = orf.TickGate(clock, PERIOD)
+    out = []
+    for k in range(1, ticks + 1):
+        dt = 3 * DT_US if SLOW_FROM <= k < SLOW_TO else DT_US
+        now = clock.now_us
+        while True:
+            clock.now_us += dt
+            if gate.fires():
+                break
+        out.append((now, clock.now_us - dt, clock.now_us))
+    return out
 
 
 def records(afa, single=False):
@@ -139,6 +163,8 @@ def script(afa, n, w0):
         lp20[12:16] = 1.0
         lp20[16:20] = 25.0
         add(OVERRIDE_AT, "onboard_state", int(g["both_flat"][0]), dict(lowpass20=lp20, last_radio_us=np.zeros(k2, np.uint64)))
+        # the time-out is `>`: a radio timer that reads exactly 1 500 000 us at tick EDGE_AT lets that tick pass, the next one panics
+        add(EDGE_AT - 2, "onboard_state", int(g["silent"][-1]), dict(last_radio_us=np.array([tick_clocks(EDGE_AT)[-1][1] - 1500000], np.uint64)))
         # PANIC is a sink: a later command to a vehicle that panicked is ignored (the flat ones keep hearing the sender)
         add(200, "telemetry", 63, 3)
         add(400, "telemetry", 0, n)
@@ -260,42 +286,45 @@ def first_tick_in_state(fields, vehicle, state):
     return None
 
 
-def synthetic_record(afa, n=N, ticks=TICKS, seed=5):
+def synthetic_record(afa, n=N, ticks=TICKS, seed=5, single=False):
     """a record like fly_device's without a device: the tick clock of 1 ms steps under a 2 ms period (3 ms in the slow stretch) and
     a made-up IMU -- gravity along the sensor's z with noise on every second vehicle (the others measure it exactly: the
-    correction axis vanishes), the spin of the turning vehicles on the gyro.  Nothing physical: the CPU tests compare restatements."""
-    plist, llist, clist = records(afa, n == 1)
-    types = np.zeros(n, np.uint8) if n == 1 else ((np.arange(n) + 2) % 3).astype(np.uint8)
+    correction axis vanishes), the spin of the turning vehicles on the gyro; vehicle NAN_FIRST measures a NaN acceleration at the
+    first tick (the alignment's cosine is a NaN, no errno: its attitude estimate is NaN for good).  Nothing physical: the CPU tests
+    compare restatements."""
+    single = single or n == 1                              # (single: the fleet of the resident grid, one tilted record for everyone)
+    plist, llist, clist = records(afa, single)
+    types = np.zeros(n, np.uint8) if single else ((np.arange(n) + 2) % 3).astype(np.uint8)
     g = groups(n)
     w0 = np.zeros((3, n), np.float32)
     w0[0, np.concatenate([g["turn"], g["turn_suppressed"]]).astype(int)] = 9.0
     rng = np.random.default_rng(seed)
     noisy = (np.arange(n) % 2 == 1)
     rec = dict(n=n, types=types, llist=llist, clist=clist, events=script(afa, n, w0), ticks=[], t0=0)
-    after = 0
-    for k in range(1, ticks + 1):
-        dt = 3 * DT_US if SLOW_FROM <= k < SLOW_TO else DT_US
-        now = after                                        # the clock behind the previous ticking step
-        T = now if dt != DT_US else now + dt               # 1 ms steps: the tick fires on the second, which starts here; 3 ms: on the first
-        after = T + dt
+    for k, (now, T, after) in enumerate(tick_clocks(ticks), start=1):
         gyro = (w0 + np.where(noisy, rng.normal(0, 0.1, (3, n)), 0.0)).astype(np.float32)
         acc = (np.array([[0.0], [0.0], [9.81]]) + np.where(noisy, rng.normal(0, 0.2, (3, n)), 0.0)).astype(np.float32)
+        if k == 1 and n > NAN_FIRST:
+            acc[:, NAN_FIRST] = np.nan
         rec["ticks"].append((now, T, after, gyro, acc))
     return rec
 
 
-def replay_scalar(afa, rec, math=oc.glibc_math, ticks=None, vehicles=None):
-    """the recorded flight through tests/onboard_reference.py, one vehicle at a time -> per tick dicts like Onboard.fields() plus
-    "motor_cmd", for `vehicles` (default: all)"""
+def drive_scalar(afa, rec, make_vehicle, ticks=None, vehicles=None, after_tick=None):
+    """THE driver of one-vehicle-at-a-time objects through the recorded flight: make_vehicle(i, t0, period, logic, cfg, mount,
+    type_index) -> an object with tests/onboard_reference.Vehicle's radio / set_battery / place / tick / telemetry.  With Vehicle
+    itself this is replay_scalar; with a recorder it is the call list the reference's own class is given
+    (tests/onboard_probe.py).  after_tick(k, fleet) is called behind the ticks of tick k.  -> (fleet, telemetry): telemetry[(k,
+    first, count)] = [what telemetry() returned, per vehicle of the range that is in the fleet]"""
     from tests import gps_imu_reference as gref
-    from tests import onboard_reference as orf
     F = np.float32
     n = rec["n"]
     who = list(range(n)) if vehicles is None else list(vehicles)
     logic = [oc.logic_record(p) for p in rec["llist"]]
     cfgs = [oc.config_from(c) for c in rec["clist"]]
     mounts = [gref.mount_matrix(*r["mount"]) for r in logic]
-    fleet = {i: orf.Vehicle(rec["t0"], PERIOD, logic[int(rec["types"][i])], cfgs[int(rec["types"][i])], mounts[int(rec["types"][i])], math) for i in who}
+    fleet = {i: make_vehicle(i, rec["t0"], PERIOD, logic[int(rec["types"][i])], cfgs[int(rec["types"][i])], mounts[int(rec["types"][i])],
+                             int(rec["types"][i])) for i in who}
 
     def deliver(event, when):
         if event[0] in ("rates", "late_rates"):
@@ -308,7 +337,7 @@ def replay_scalar(afa, rec, math=oc.glibc_math, ticks=None, vehicles=None):
                 if event[1] + j in fleet:
                     fleet[event[1] + j].radio(when, mtype[j], flags[j], floats[:, j])
 
-    out = []
+    telemetry = {}
     for k, (now, T, after, gyro, acc) in enumerate(rec["ticks"][:ticks], start=1):
         late = []
         for event in rec["events"].get(k, []):
@@ -319,40 +348,45 @@ def replay_scalar(afa, rec, math=oc.glibc_math, ticks=None, vehicles=None):
             elif event[0] == "battery":
                 for j, v in enumerate(event[2]):
                     if event[1] + j in fleet:
-                        fleet[event[1] + j]._battVoltage = F(v)
+                        fleet[event[1] + j].set_battery(F(v))
             elif event[0] == "onboard_state":
                 for j in range(np.asarray(next(iter(event[2].values()))).shape[-1]):
                     if event[1] + j not in fleet:
                         continue
-                    L = fleet[event[1] + j].logic
                     for name, a in event[2].items():
-                        a = np.asarray(a)
-                        if name == "est_att4":
-                            L._kf._att = [F(x) for x in a[:, j]]
-                        elif name == "last_radio_us":
-                            L._timeSinceLastRadioMessage.last = int(a[j])
-                        elif name == "lowpass20":
-                            col = a[:, j].astype(F)
-                            L._acc.xm0, L._acc.xm1, L._acc.ym0, L._acc.ym1 = (list(col[3 * m:3 * m + 3]) for m in range(4))
-                            L._batt.xm0, L._batt.xm1, L._batt.ym0, L._batt.ym1 = col[12:16]
-                            L._temp.xm0, L._temp.xm1, L._temp.ym0, L._temp.ym1 = col[16:20]
-                        else:
-                            raise ValueError(name)
-        row = {}
+                        fleet[event[1] + j].place(name, np.asarray(a)[..., j])
         for i, veh in fleet.items():
-            cmd = veh.tick(T, gyro[:, i], acc[:, i])
-            L = veh.logic
-            row[i] = dict(flight_state=L._state, panic_reason=L._firstPanicReason, warnings=L._telWarnings, est_att=np.array(L._kf._att, F),
-                          est_ang_vel=np.array(L._kf._angVel, F), acc_filtered=np.array(L._acc.GetValue(), F), batt_filtered=F(L._voltageFiltered),
-                          main_loop_dt=F(L._monitorMainLoopPeriod.lpDt), cmd_dt=F(L._monitorCmdRate.lpDt),
-                          motor_forces=np.array(L._desMotorForcesForTelemetry, F), cycle_counter=L._cycleCounter,
-                          last_radio_us=L._timeSinceLastRadioMessage.last, motors_running=int(L.GetAreMotorsRunning()), motor_cmd=np.array(cmd, F))
+            veh.tick(T, gyro[:, i], acc[:, i])
+        if after_tick is not None:
+            after_tick(k, fleet)
         for event in late:
             deliver(event, after)
         for event in rec["events"].get(k, []):
             if event[0] == "telemetry":                          # GetTelemetryDataPackets clears the warnings of the range
-                for j in range(event[2]):
-                    if event[1] + j in fleet:
-                        fleet[event[1] + j].logic._telWarnings = 0
+                telemetry[(k, event[1], event[2])] = {event[1] + j: fleet[event[1] + j].telemetry() for j in range(event[2]) if event[1] + j in fleet}
+    return fleet, telemetry
+
+
+def replay_scalar(afa, rec, math=oc.glibc_math, ticks=None, vehicles=None, with_telemetry=False):
+    """the recorded flight through tests/onboard_reference.py, one vehicle at a time -> per tick dicts like Onboard.fields() plus
+    "motor_cmd", for `vehicles` (default: all); with_telemetry: -> (rows, {(k, first, count): {vehicle: (packet 1, packet 2)}})"""
+    from tests import onboard_reference as orf
+    F = np.float32
+    out = []
+
+    def after_tick(k, fleet):
+        row = {}
+        for i, veh in fleet.items():
+            L = veh.logic
+            row[i] = dict(flight_state=L._state, panic_reason=L._firstPanicReason, warnings=L._telWarnings, est_att=np.array(L._kf._att, F),
+                          est_ang_vel=np.array(L._kf._angVel, F), acc_filtered=np.array(L._acc.GetValue(), F),
+                          gyro_filtered=np.array(L._gyro.GetValue(), F), temp_filtered=F(L._temp.GetValue()), batt_filtered=F(L._voltageFiltered),
+                          main_loop_dt=F(L._monitorMainLoopPeriod.lpDt), cmd_dt=F(L._monitorCmdRate.lpDt),
+                          motor_forces=np.array(L._desMotorForcesForTelemetry, F), cycle_counter=L._cycleCounter,
+                          last_radio_us=L._timeSinceLastRadioMessage.last, motors_running=int(L.GetAreMotorsRunning()),
+                          motor_cmd=np.array(L._desMotorSpeeds, F))
         out.append(row)
-    return out
+
+    _, telemetry = drive_scalar(afa, rec, lambda i, t0, period, logic, cfg, mount, ty: orf.Vehicle(t0, period, logic, cfg, mount, math),
+                                ticks, vehicles, after_tick)
+    return (out, telemetry) if with_telemetry else out

@@ -1,13 +1,22 @@
 """Onboard::QuadcopterLogic and the complementary branch of Onboard::KalmanFilter6DOF restated line by line in scalar Python,
 quirks included, for ONE vehicle without UWB ranging (Components/Components/Logic/QuadcopterLogic.{hpp,cpp},
-KalmanFilter6DOF.cpp:33-147, Common/Time/Timer.hpp, Common/Math/LowPassFilter{First,Second}Order.hpp, Rotation.hpp, Vec3.hpp), with the
-part of Simulation::Quadcopter_T::Run that feeds it (Quadcopter_T.cpp:163-185).  Every value is a numpy float32 scalar, so every
-operation rounds as the reference's float code does; math(op, x[, x2]) is tests/onboard_checker.py's (sinf, cosf, acosf, asinf, atan2f).
+KalmanFilter6DOF.cpp:33-147, Common/Time/Timer.hpp, Common/Math/LowPassFilter{First,Second}Order.hpp, Rotation.hpp, Vec3.hpp,
+Common/DataTypes/TelemetryPacket.hpp), with the part of Simulation::Quadcopter_T::Run that feeds it (Quadcopter_T.cpp:159-185).
+Every value is a numpy float32 scalar, so every operation rounds as the reference's float code does; math(op, x[, x2]) is
+tests/onboard_checker.py's (sinf, cosf, acosf, asinf, atan2f).
 
 The classes keep the reference's names.  Not restated: UWB (no network exists in Rappids_Simulator), FS_FULLY_AUTONOMOUS's
 controller, TestMotors, the calibrations.  tests/onboard_checker.py is the same in numpy for N vehicles; tests/test_onboard_cpu.py
-holds the two to each other bit for bit.  UNPINNED: the class is compiled nowhere here (QuadcopterLogic.hpp pulls in the 9x9
-Eigen filter)."""
+holds the two to each other bit for bit.
+
+PINNED to the reference's own class: oracle/_ref/onboard_probe compiles QuadcopterLogic.cpp and KalmanFilter6DOF.cpp where they lie
+(against oracle/eigen_trap, whose Eigen arithmetic aborts by name: the path restated here executes none) and is given, call for
+call, what this restatement is given on the scripted flight of tests/onboard_flight.py; tests/golden/make_onboard_reference.py
+asserts every field of every vehicle after every tick and every telemetry byte equal bit for bit, and
+tests/test_onboard_reference.py holds this file to what it recorded (tests/golden/onboard_reference.npz).  The feed
+(Vehicle, TickGate) is pinned by the probe's vehicle mode, Quadcopter_T<Onboard::QuadcopterLogic> itself.  STILL OPEN: the
+branch behind _UWBInitialized, RunControllerFullyAutonomous, TestMotors and the calibrations (they would abort the probe by
+name or are not driven)."""
 import numpy as np
 
 from tests.onboard_checker import lp1_coefficient            # (libm's expf through ctypes: one spelling of a library call)
@@ -182,6 +191,17 @@ def to_euler_ypr(q, math):                                      # :163-169
     return y, p, r
 
 
+def MapToOnesRange(x, a, b):                                    # TelemetryPacket.hpp:39-41 (a, b ints: b - a in int, then float)
+    return ((F(x) - F(a)) / F(b - a)) * F(2) - F(1)
+
+
+def EncodeOnesRange(t):                                         # :55-63; a NaN passes both tests, and its conversion to uint16 is 0 on x86-64
+    with np.errstate(all="ignore"):
+        if t < -1 or t > 1 or np.isnan(t):
+            return 0
+        return int(F(32768) + F(32767) * t) & 0xffff
+
+
 def acosf_errno(c, math):
     """errno = 0; angle = acosf(c); if (errno) angle = c < 0 ? float(M_PI) : 0 -- glibc sets EDOM for |c| > 1, not for a NaN"""
     if c > F(1) or c < F(-1):
@@ -277,25 +297,32 @@ class QuadcopterLogic:
         self._msgNew, self._msgType, self._msgFlags, self._msgFloats = False, 0, 0, [F(0)] * 4
         self._voltageFiltered = F(0)
         self._voltageRaw = F(0)
+        self._debug = [F(0)] * 6
+        self._count = dict(batt=0, gyro=0, acc=0, temp=0)       # _battMeas.count, _imuRateGyro.count, ...
 
     def _rotate(self, v):                                       # _R * Vec3f, Vec3.hpp:201-210
         R = self._R
         return [((F(0) + R[i][0] * F(v[0])) + R[i][1] * F(v[1])) + R[i][2] * F(v[2]) for i in range(3)]
 
     def SetBatteryMeasurement(self, voltage):
+        self._count["batt"] += 1
         self._voltageRaw = F(voltage)
         self._voltageFiltered = self._batt.Apply(voltage)
 
     def SetIMUMeasurementRateGyro(self, x, y, z):
+        self._count["gyro"] += 1
         with np.errstate(all="ignore"):
             raw = self._rotate([x, y, z])
             self._gyro.Apply([raw[0] - F(0), raw[1] - F(0), raw[2] - F(0)])
 
     def SetIMUMeasurementAccelerometer(self, x, y, z):
+        self._count["acc"] += 1
         with np.errstate(all="ignore"):
             self._acc.Apply(self._rotate([x, y, z]))
 
     def SetIMUMeasurementTemperature(self, t):
+        self._count["temp"] += 1
+        self._tempRaw = F(t)
         self._temp.Apply(t)
 
     def SetRadioMessage(self, mtype, flags, floats):
@@ -305,6 +332,21 @@ class QuadcopterLogic:
 
     def GetAreMotorsRunning(self):
         return any(s > 0 for s in self._desMotorSpeeds)
+
+    def GetTelemetryDataPackets(self):                          # :621-679, EncodeTelemetryPacket (TelemetryPacket.hpp:122-166) -> 2 x 30 bytes
+        code = lambda x, a, b: EncodeOnesRange(MapToOnesRange(x, a, b))      # noqa: E731
+        acc, gyro, q = self._acc.GetValue(), self._gyro.GetValue(), self._kf._att
+        vec = [q[1], q[2], q[3]] if q[0] > 0 else [-q[1], -q[2], -q[3]]       # ToVectorPartOfQuaternion, Rotation.hpp:155-161
+        with np.errstate(all="ignore"):
+            d1 = [code(v, -30, 30) for v in acc] + [code(v, -35, 35) for v in gyro] + [code(v, 0, 10) for v in self._desMotorForcesForTelemetry] + \
+                 [code(F(0), -30, 30)] * 3 + [code(self._voltageRaw, 0, 15)]
+            d2 = [code(F(0), -30, 30)] * 3 + [code(v, -1, 1) for v in vec] + [code(v, -100, 100) for v in self._debug]
+        number = self._telPacketCounter % 256
+        p1 = bytes([0, number]) + b"".join(int(c).to_bytes(2, "little") for c in d1)
+        p2 = bytes([1, number]) + b"".join(int(c).to_bytes(2, "little") for c in d2) + bytes([self._firstPanicReason, 0, self._telWarnings, 0])
+        self._telPacketCounter += 1
+        self._telWarnings = 0
+        return p1, p2
 
     def Run(self):                                              # :164-219
         self._cycleCounter += 1
@@ -359,6 +401,7 @@ class QuadcopterLogic:
             if self._state != FS_PANIC:
                 self._state = FS_PANIC
                 self._firstPanicReason = unsafeReason
+        self._debug[0] = self._temp.GetValue()                  # :178
         # the controller
         with np.errstate(all="ignore"):
             if self._state == FS_EXTERNAL_ACCELERATION_CONTROL:
@@ -434,8 +477,24 @@ class QuadcopterLogic:
         return [nk3 * desRotVec[k] - kr * ax[k] for k in range(3)]
 
 
+class TickGate:
+    """when Quadcopter_T::Run runs the logic (Quadcopter_T.cpp:159-160): a Timer read in DOUBLE seconds against the double period,
+    then moved on by AdjustTimeBySeconds<double>(-period), which truncates period * 1e6 to whole microseconds"""
+
+    def __init__(self, clock, period):
+        self.clock, self.period, self.last = clock, float(period), clock.now_us
+
+    def fires(self):
+        if float((self.clock.now_us - self.last) & U64) * 1e-6 > self.period:
+            self.last = (self.last + int(-self.period * -1e6)) & U64
+            return True
+        return False
+
+
 class Vehicle:
-    """what Quadcopter_T::Run does at a logic tick (Quadcopter_T.cpp:163-185), the clock set by the caller"""
+    """what Quadcopter_T::Run does at a logic tick (Quadcopter_T.cpp:163-185), the clock set by the caller; radio, tick, place
+    and telemetry are every way tests/onboard_flight.drive_scalar touches a vehicle (a recorder with the same four methods
+    turns the drive into the call list oracle/_ref/onboard_probe is given)"""
 
     def __init__(self, t0_us, period, logic, cfg, R, math):
         self.clock = Clock(t0_us)
@@ -445,6 +504,33 @@ class Vehicle:
     def radio(self, now_us, mtype, flags, floats):
         self.clock.now_us = int(now_us)
         self.logic.SetRadioMessage(mtype, flags, floats)
+
+    def set_battery(self, volts):
+        self._battVoltage = F(volts)
+
+    def place(self, name, value):
+        """afe_onboard_set_state's fields written into the members they stand for"""
+        L = self.logic
+        if name == "est_att4":
+            L._kf._att = [F(x) for x in value]
+        elif name == "est_ang_vel3":
+            L._kf._angVel = [F(x) for x in value]
+        elif name == "imu_initialized":
+            L._kf._IMUInitialized = bool(value)
+        elif name == "flight_state":
+            L._state = int(value)
+        elif name == "last_radio_us":
+            L._timeSinceLastRadioMessage.last = int(value)
+        elif name == "lowpass20":
+            col = np.asarray(value, F)
+            L._acc.xm0, L._acc.xm1, L._acc.ym0, L._acc.ym1 = (list(col[3 * m:3 * m + 3]) for m in range(4))
+            L._batt.xm0, L._batt.xm1, L._batt.ym0, L._batt.ym1 = col[12:16]
+            L._temp.xm0, L._temp.xm1, L._temp.ym0, L._temp.ym1 = col[16:20]
+        else:
+            raise ValueError(name)
+
+    def telemetry(self):
+        return self.logic.GetTelemetryDataPackets()
 
     def tick(self, T_us, gyro, acc):
         self.clock.now_us = int(T_us)
