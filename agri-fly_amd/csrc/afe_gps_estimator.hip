@@ -7,8 +7,10 @@
 //
 // THE DEFINITION is Components/Components/Offboard/GPSIMUStateEstimator.cpp, restated line by line in scalar Python
 // (tests/gps_imu_reference.py) and in numpy (tests/gps_estimator_checker.py); kernels and checker must give the same bits,
-// so the ORDER of the operations is part of the contract.  The reference class is not compiled anywhere in this project (it
-// needs Eigen): this is a restatement, not a pin.  Everything is double, IEEE, uncontracted; + - * / sqrt and the
+// so the ORDER of the operations is part of the contract.  The class's own text is compiled where it lies by the test
+// infrastructure's probe, against a recording dense stand-in for Eigen, and tests/test_gps_reference.py holds the
+// restatement to what it recorded (tests/golden/gps_reference.npz): bit for bit outside Eigen, branch and finite /
+// non-finite mask exactly, Eigen's finite results within derived bounds.  Everything is double, IEEE, uncontracted; + - * / sqrt and the
 // conversions are correctly rounded on gfx950 and in numpy.  Only sin, cos and acosf are the device library's own:
 // afe_gps_estimator_selftest_math evaluates the very helpers the kernels call.
 //
@@ -23,22 +25,38 @@
 //   * Vec3d(0, 0, -9.81f) (:117) is the float constant widened; the x and y sums with +0 are made.
 //   * _lastMeasUpdateAttCorrection.z / 2.0f (:176-190) is a double division by 2.
 //   * _lastMeasUpdateAttCorrection is not set by the constructor nor by Reset(): a Vec3d starts as NaN (Vec3.hpp:34-38).
-//     The first ordinary Predict therefore makes the attitude block of the covariance NaN, two more carry it through the
-//     velocity to the position block, and the update that finds it takes the singular branch; from there the filter runs.
+//     The first ordinary Predict therefore makes the attitude rows and columns of the covariance NaN; the reference's
+//     products are dense (NON-FINITE NUMBERS below), so the second makes all 81 entries NaN, and an update behind either
+//     takes the singular branch; from there the filter runs.  (An update behind the alignment alone, with no ordinary
+//     Predict between, is an ordinary update and overwrites the NaN correction: such a filter never restarts.)
 //   * dt = _estimateTimer.GetSeconds<double>() (:107) is double(now_us - last_us) * 1e-6 (Timer.hpp:36-50).
 //   * the first Predict calls Reset(), aligns the attitude to the measured gravity and returns (:67-103); an
 //     UpdateWithMeasurement that arrives first sets _initialized, so the alignment never happens (:208-217).
 //   * Rotationd::FromRotationVector, FromAxisAngle, Inverse, operator* and GetRotationMatrix as in Rotation.hpp (:66-97,
 //     :124-137, :196-220), Rotate as :234-243.
 //
-// EVALUATION ORDER (Eigen's cannot be known here, so the definition fixes one).
+// NON-FINITE NUMBERS are the dense algebra's.  f * _cov * f.transpose() (:195), H * (_cov * H.transpose()) (:224) and
+//   (I - L H) * _cov (:255) are dense products in any evaluation by Eigen: they multiply by the structural zeros of f, H and
+//   I - L H too, and 0 * NaN = 0 * Inf = NaN, whatever the order of summation.  So a covariance with ANY entry that is not
+//   finite ("tainted") is non-finite in all 81 places after the next Predict, whatever f holds, and makes every entry of S
+//   non-finite at the next UpdateWithMeasurement, which then takes :230-236.  The definition: a tainted covariance becomes
+//   NaN everywhere in Predict (the dense product keeps an infinity at (i, j) for a lone infinity at (k, l) where f(i, k) and
+//   f(j, l) are both non-zero; the mask is the same and nothing reads the difference before the restart), and a tainted
+//   covariance is singular in the update.  For an untainted covariance the sparse order below and the dense products have
+//   the same finite / non-finite mask (a non-finite entry of f or L meets every entry of its row either way), and the
+//   finite bits are those of the sparse order; a zero keeps the sign the sparse order gives it (the dense sum's depends on
+//   Eigen's order).  The kernels keep "tainted" as bit 1 of the per-vehicle `initialized` word: set where they store an
+//   entry that is not finite, cleared by ResetVariance, recomputed by set_state when it is given a covariance.
+//
+// EVALUATION ORDER for finite numbers (Eigen's cannot be known here, so the definition fixes one).
 //   Covariance prediction (:195): F = I + N, N the structurally non-zero off-identity entries of :133-191 (three dt, nine
 //   of the velocity/attitude block, six off-diagonal of the attitude/attitude block).  T[i][j] = P[i][j] + sum_k N[i][k]
 //   P[k][j], k ascending over row i's non-zeros, added left to right; C[i][j] = T[i][j] + sum_k T[i][k] N[j][k], k ascending
 //   over row j's non-zeros; then the process noise as :197-202 writes it.
 //   Update (:219-256): S = P[0:3][0:3] + sigma^2 I (the off-diagonal sums with +0 are made); det by cofactors along the
 //   first row; Sinv = adj(S) (1 / det) entry by entry; L = P[:,0:3] Sinv, dx = L dpos, C = P - L P[0:3][:], each with k
-//   ascending, (a b + c d) + e f; then 0.5 (C + C').  Singular (|det| < 1e-10 or an entry of S not finite): :230-236.
+//   ascending, (a b + c d) + e f; then 0.5 (C + C').  Singular (|det| < 1e-10, an entry of S not finite, or a
+//   tainted covariance): :230-236.
 //
 // THE SAMPLE is what the simulator's GetAccelerometer / GetRateGyro return (Quadcopter_T.hpp:75-82): the logic's low-passed,
 // mount-rotated values (QuadcopterLogic.hpp:40-52, :71-77).  The gyro value is the engine's own filter output (the ym1 rows
@@ -52,7 +70,7 @@
 // est[13] (pos 3, vel 3, att 4, angVel 3), two rows of +0 (so that est looks like an fp64 engine's slabs to the follower),
 // cov[81] row major, corr[3] (_lastMeasUpdateAttCorrection), the time of the last Predict and of the last good update
 // (uint64 us), and the accelerometer filter's xm0, xm1, ym0, ym1 (3 floats each: 12 float rows in 6 rows of words).
-// initialized and numResets are a slab of 4-byte words.
+// initialized and numResets are a slab of 4-byte words; bit 0 of the first is _initialized, bit 1 "tainted".
 //
 // THE COVARIANCE IN PLACE.  Predict holds the three old attitude rows (27 doubles) and walks the pairs of position row i and
 // velocity row 3 + i (the position row needs its own row and the old velocity row, which is loaded once and then serves
@@ -78,6 +96,7 @@ constexpr int kEstWords = 13, kCovWords = 81;
 // rows of the one slab of 8-byte words (GpsArgs::slab, `stride` words a row) and of the one of 4-byte words (GpsArgs::flags)
 constexpr int kRowEst = 0, kRowZero = 13, kRowCov = 15, kRowCorr = 96, kRowTPredict = 99, kRowTUpdate = 100, kRowLpf = 101, kRowEnd = 107;
 constexpr int kFlagInit = 0, kFlagResets = 1, kFlagWords = 2;
+constexpr uint32_t kInitBit = 1u, kTaintBit = 2u;        // of the kFlagInit word (NON-FINITE NUMBERS above)
 constexpr double kMinAngle = 4.84813681e-6;              // Rotation.hpp: one arc second
 
 // ---- the device library's functions, through the helpers both the kernels and the self-test call --------------------------
@@ -275,7 +294,8 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_imu_kernel(GpsArgs g
   }
   unsigned long long *T = (unsigned long long *)g.slab;
   double *E = g.slab + kRowEst * S;
-  if (g.flags[kFlagInit * S + v] == 0) {                                  // :67-103
+  const uint32_t word = g.flags[kFlagInit * S + v];
+  if (word == 0) {                                                        // :67-103
     V3 zero;
     zero.x = zero.y = zero.z = 0.0;
     State s = fresh_state(zero);                                          // Reset()
@@ -283,7 +303,7 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_imu_kernel(GpsArgs g
     T[kRowTPredict * S + v] = now_us;
     T[kRowTUpdate * S + v] = now_us;
     g.flags[kFlagResets * S + v] = g.flags[kFlagResets * S + v] + 1u;
-    g.flags[kFlagInit * S + v] = 1;
+    g.flags[kFlagInit * S + v] = kInitBit;
     double R[9];
     q_matrix(q_inv(s.q), R);
     V3 e3;
@@ -340,6 +360,11 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_imu_kernel(GpsArgs g
     K[0] = 0.0; K[S] = 0.0; K[2 * S] = 0.0;                               // :192
   }
   // ---- the covariance in place (:195-202)
+  // a tainted covariance: NaN in all 81 places (the lane computes as the others do and stores NaN); an untainted one
+  // becomes tainted by the first entry stored that is not finite
+  const bool taint = (word & kTaintBit) != 0;
+  const double nan = __builtin_nan("");
+  bool bad = false;
   double *C = g.slab + kRowCov * S + v;
   double A[3][9];
 #pragma unroll
@@ -356,13 +381,13 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_imu_kernel(GpsArgs g
     for (int j = 0; j < 9; j++) t[j] = C[(9 * i + j) * S] + dt * V[j];
     c_row(t, dt, nv, na, c);
 #pragma unroll
-    for (int j = 0; j < 9; j++) C[(9 * i + j) * S] = c[j];
+    for (int j = 0; j < 9; j++) { bad = bad || !isfinite(c[j]); C[(9 * i + j) * S] = taint ? nan : c[j]; }
 #pragma unroll
     for (int j = 0; j < 9; j++) t[j] = ((V[j] + nv[i][0] * A[0][j]) + nv[i][1] * A[1][j]) + nv[i][2] * A[2][j];
     c_row(t, dt, nv, na, c);
     c[3 + i] = c[3 + i] + pn_v;
 #pragma unroll
-    for (int j = 0; j < 9; j++) C[(9 * (3 + i) + j) * S] = c[j];
+    for (int j = 0; j < 9; j++) { bad = bad || !isfinite(c[j]); C[(9 * (3 + i) + j) * S] = taint ? nan : c[j]; }
   }
   {                                                                       // attitude rows
     double t[3][9];
@@ -378,9 +403,10 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_imu_kernel(GpsArgs g
       c_row(t[r], dt, nv, na, c);
       c[6 + r] = c[6 + r] + pn_a;
 #pragma unroll
-      for (int j = 0; j < 9; j++) C[(9 * (6 + r) + j) * S] = c[j];
+      for (int j = 0; j < 9; j++) { bad = bad || !isfinite(c[j]); C[(9 * (6 + r) + j) * S] = taint ? nan : c[j]; }
     }
   }
+  if (bad && !taint) g.flags[kFlagInit * S + v] = kInitBit | kTaintBit;
 }
 
 // UpdateWithMeasurement(the engine's position)
@@ -397,7 +423,8 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_measure_kernel(GpsAr
   }
   double *E = g.slab + kRowEst * S;
   double *C = g.slab + kRowCov * S + v;
-  bool reinit = g.flags[kFlagInit * S + v] == 0;                          // :208-217
+  const uint32_t word = g.flags[kFlagInit * S + v];
+  bool reinit = word == 0;                                                // :208-217
   bool singular = false;
   double P0[3][9];
   double det = 0.0, co[3][3];
@@ -407,7 +434,7 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_measure_kernel(GpsAr
 #pragma unroll
       for (int j = 0; j < 9; j++) P0[i][j] = C[(9 * i + j) * S];
     double Sm[3][3];
-    bool finite = true;
+    bool finite = (word & kTaintBit) == 0;                                // dense: a tainted covariance makes S non-finite
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -435,11 +462,12 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_measure_kernel(GpsAr
     if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicAdd(g.counter, (unsigned long long)__popcll(mask));
   }
   if (reinit) {                                                           // :209-216, :230-236
-    g.flags[kFlagInit * S + v] = 1;
+    if (word != kInitBit) g.flags[kFlagInit * S + v] = kInitBit;          // ResetVariance() clears the taint
     store_est(E, S, v, fresh_state(meas));
     store_fresh_cov(g, v);
     return;
   }
+  bool bad = false;                                                       // an entry stored that is not finite taints
   const double rdet = 1 / det;
   double Si[3][3];
 #pragma unroll
@@ -462,6 +490,7 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_measure_kernel(GpsAr
         const double cki = P0[k][i] - ((L[k][0] * P0[0][i] + L[k][1] * P0[1][i]) + L[k][2] * P0[2][i]);
         const double cik = p[k] - ((L[i][0] * P0[0][k] + L[i][1] * P0[1][k]) + L[i][2] * P0[2][k]);
         const double sym = 0.5 * (cki + cik);
+        bad = bad || !isfinite(sym);
         C[(9 * k + i) * S] = sym; C[(9 * i + k) * S] = sym;
       }
     }
@@ -489,6 +518,7 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_measure_kernel(GpsAr
       const double cij = P0[i][j] - ((L[i][0] * P0[0][j] + L[i][1] * P0[1][j]) + L[i][2] * P0[2][j]);
       const double cji = P0[j][i] - ((L[j][0] * P0[0][i] + L[j][1] * P0[1][i]) + L[j][2] * P0[2][i]);
       const double sym = 0.5 * (cij + cji);
+      bad = bad || !isfinite(sym);
       C[(9 * i + j) * S] = sym; C[(9 * j + i) * S] = sym;
     }
 #pragma unroll
@@ -499,16 +529,26 @@ __global__ void __launch_bounds__(kBlock) afe_gps_estimator_measure_kernel(GpsAr
       const double cij = pij - ((L[i][0] * P0[0][j] + L[i][1] * P0[1][j]) + L[i][2] * P0[2][j]);
       const double cji = pji - ((L[j][0] * P0[0][i] + L[j][1] * P0[1][i]) + L[j][2] * P0[2][i]);
       const double sym = 0.5 * (cij + cji);
+      bad = bad || !isfinite(sym);
       C[(9 * i + j) * S] = sym; C[(9 * j + i) * S] = sym;
     }
+  if (bad) g.flags[kFlagInit * S + v] = kInitBit | kTaintBit;
   ((unsigned long long *)g.slab)[kRowTUpdate * S + v] = now_us;          // :257
 }
 
-// set_state: mark vehicles [first, first + count) initialised
-__global__ void __launch_bounds__(kBlock) afe_gps_estimator_mark_kernel(GpsArgs g, int64_t first, int64_t count) {
+// set_state: mark vehicles [first, first + count) initialised; with a covariance given, tainted is what that covariance says
+__global__ void __launch_bounds__(kBlock) afe_gps_estimator_mark_kernel(GpsArgs g, int64_t first, int64_t count, int have_cov) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= count) return;
-  g.flags[kFlagInit * g.stride + first + i] = 1;
+  const int64_t S = g.stride, v = first + i;
+  uint32_t taint = g.flags[kFlagInit * S + v] & kTaintBit;
+  if (have_cov) {
+    const double *C = g.slab + kRowCov * S + v;
+    bool bad = false;
+    for (int k = 0; k < kCovWords; k++) bad = bad || !isfinite(C[k * S]);
+    taint = bad ? kTaintBit : 0u;
+  }
+  g.flags[kFlagInit * S + v] = kInitBit | taint;
 }
 
 __global__ void __launch_bounds__(kBlock) afe_gps_estimator_math_kernel(int op, int64_t n, const double *x, double *y) {
@@ -770,7 +810,7 @@ extern "C" int afe_gps_estimator_set_state(afe_gps_estimator *est, int64_t first
       (cov81 && !put_rows(g.slab + kRowCov * S, 8, kCovWords, S, first, count, cov81)) ||
       (corr3 && !put_rows(g.slab + kRowCorr * S, 8, 3, S, first, count, corr3)))
     return AFE_ERR_HIP;
-  hipLaunchKernelGGL(afe_gps_estimator_mark_kernel, grid_for(count), dim3(kBlock), 0, en.stream, en.g, first, count);
+  hipLaunchKernelGGL(afe_gps_estimator_mark_kernel, grid_for(count), dim3(kBlock), 0, en.stream, en.g, first, count, cov81 ? 1 : 0);
   return launched() ? AFE_OK : AFE_ERR_HIP;
 }
 

@@ -1087,7 +1087,9 @@ int afe_gps_estimator_info(const afe_gps_estimator *g, int64_t *n_vehicles, uint
  * previous _imu (the first call needs at least one tick); afe_steps_until_tick says how far to step.  Does not wait. */
 int afe_gps_estimator_imu(afe_gps_estimator *g);
 /* UpdateWithMeasurement(the engine's position now) (:206-258).  n_reinitialised: the vehicles that took the singular
- * branch (:228-237) in this call; NULL: nothing is downloaded and the call does not wait. */
+ * branch (:228-237) in this call; NULL: nothing is downloaded and the call does not wait.  The reference's products are
+ * dense: a covariance with ANY entry that is not finite makes S non-finite and takes that branch, and is NaN everywhere
+ * after a Predict (afe_gps_estimator.hip, NON-FINITE NUMBERS). */
 int afe_gps_estimator_measure(afe_gps_estimator *g, int64_t *n_reinitialised);
 /* Planar [comps][count]: est13 (pos 3, vel 3, att 4, ang_vel 3), cov81 (row major, all 81 words: after a Predict the
  * matrix is symmetric in value but not in bits), the times of the last Predict and of the last good update, initialized,

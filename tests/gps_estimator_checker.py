@@ -139,8 +139,17 @@ def _c_row(t, dt, nv, na):
     return c
 
 
+def tainted(P):
+    """vehicles whose covariance has an entry that is not finite (gps_imu_reference.tainted); P [9, 9, n]"""
+    return ~np.isfinite(P).all((0, 1))
+
+
 def predict_covariance(P, dt, nv, na):
-    """F P F' of GPSIMUStateEstimator.cpp:195 in the order the definition fixes; P [9, 9, n]"""
+    """F P F' of GPSIMUStateEstimator.cpp:195 in the order the definition fixes, NaN everywhere for a tainted P; P [9, 9, n]"""
+    return np.where(tainted(P), np.nan, _predict_finite(P, dt, nv, na))
+
+
+def _predict_finite(P, dt, nv, na):
     A = [P[6], P[7], P[8]]
     rows = []
     for i in range(3):
@@ -163,6 +172,11 @@ def innovation(P, r):
     return [[a, b, c], [d, e, f], [g, h, i]], det, adj
 
 
+# the branch a call took, per vehicle (Estimator.last_branch; tests/test_gps_reference.py holds it to the reference's)
+CALL_BRANCHES = ("first_predict", "predict", "measure_before_predict", "singular_nonfinite", "singular_tiny", "update", "reset")
+NO_CALL = 255
+
+
 class Estimator:
     """GPSIMUStateEstimator for n vehicles.  imu = Predict, measure = UpdateWithMeasurement."""
 
@@ -176,6 +190,7 @@ class Estimator:
         self.t_predict, self.t_update = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         self.initialized = np.zeros(n, bool)
         self.num_resets = np.zeros(n, np.uint32)
+        self.last_branch = np.full(n, NO_CALL, np.uint8)       # index into CALL_BRANCHES of the latest call's branch
         self._reset(np.ones(n, bool), 0)
 
     def _fresh_cov(self, who):
@@ -204,6 +219,7 @@ class Estimator:
         who = np.zeros(self.n, bool)
         who[first:self.n if count is None else first + count] = True
         self._reset(who, now_us)
+        self.last_branch = np.where(who, 6, NO_CALL).astype(np.uint8)
 
     def set_state(self, est=None, cov=None, corr=None, first=0):
         k = next(a for a in (est, cov, corr) if a is not None).shape[1]
@@ -228,6 +244,7 @@ class Estimator:
     def _imu(self, now_us, a, w):
         c, n = self.cfg, self.n
         first = ~self.initialized
+        self.last_branch = np.where(first, 0, 1).astype(np.uint8)
         if first.any():                                          # :67-103
             self._reset(first, now_us)
             self.initialized[first] = True
@@ -271,7 +288,7 @@ class Estimator:
         first = ~self.initialized
         self.count["measure_before_predict"] += int(first.sum())
         S, det, adj = innovation(self.cov, c["sigma_pos"] * c["sigma_pos"])
-        finite = np.ones(self.n, bool)
+        finite = ~tainted(self.cov)
         for i in range(3):
             for j in range(3):
                 finite &= np.isfinite(S[i][j])
@@ -280,6 +297,7 @@ class Estimator:
         self.count["singular_nonfinite"] += int((singular & ~finite).sum())
         go = ~first & ~singular
         self.count["update"] += int(go.sum())
+        self.last_branch = np.where(first, 2, np.where(singular, np.where(finite, 4, 3), 5)).astype(np.uint8)
         r = 1 / det
         Si = [[adj[i][j] * r for j in range(3)] for i in range(3)]
         P = self.cov
@@ -348,15 +366,61 @@ def make_script(n):
     return ev
 
 
+# ---- the phase groups: 0 to 5 ordinary Predicts between the alignment and the first measurement -----------------------------------
+# A 500 Hz IMU and a 100 Hz GPS that start out of phase.  Vehicle v is in group (v + shift) % 6; group g is Reset() before
+# every tick up to tick 6 - g (a Reset() leaves _lastMeasUpdateAttCorrection the NaN the constructor left, so the vehicle
+# keeps aligning and makes no ordinary Predict), aligns for the last time at tick 6 - g, makes g ordinary Predicts and meets
+# the measurement behind tick 6.  Groups 1 to 5 find a covariance the NaN correction has tainted and restart; group 0
+# makes an ordinary update, which overwrites the correction.  Three offboard periods follow.
+PHASE_GROUPS = 6
+PHASE_FIRST_MEASURE = 11                                            # the index of that measurement in make_phase_script
+
+
+def phase_group(n, shift=0):
+    return (np.arange(n) + shift) % PHASE_GROUPS
+
+
+def phase_ranges(n, shift, upto):
+    """[(first, count)] covering the vehicles of groups 0 .. upto"""
+    who = phase_group(n, shift) <= upto
+    edges = np.flatnonzero(np.diff(np.concatenate([[0], who.astype(int), [0]])))
+    return [(int(a), int(b - a)) for a, b in zip(edges[0::2], edges[1::2])]
+
+
+def make_phase_script(n, shift=0):
+    """events as make_script's, and ("reset_ranges", [(first, count), ...])"""
+    ev = [("imu",)]
+    for tick in range(2, PHASE_GROUPS + 1):
+        ev += [("reset_ranges", phase_ranges(n, shift, PHASE_GROUPS - tick)), ("imu",)]
+    ev += [("measure",)]
+    assert len(ev) - 1 == PHASE_FIRST_MEASURE
+    return ev + ([("imu",)] * 5 + [("measure",)]) * 3
+
+
+# the single non-finite covariance entries: a diagonal and an off-diagonal place in each of the six blocks (pos/pos, pos/vel,
+# pos/att, vel/vel, vel/att, att/att; the blocks below the diagonal by the transposed place), each with NaN, +Inf and -Inf
+POISON_PLACES = ((0, 0), (1, 2), (0, 3), (4, 2), (1, 7), (8, 0), (4, 4), (3, 5), (5, 8), (6, 4), (7, 7), (8, 6))
+POISON_VALUES = (np.nan, np.inf, -np.inf)
+N_POISON = len(POISON_PLACES) * len(POISON_VALUES)
+
+
 def payload(kind, count, near):
     """set_state's arrays: (est13, cov81, corr3).  near [3, count]: where the vehicles are, roughly"""
-    rng = np.random.default_rng({"tiny": 1, "inf": 2, "far": 3, "sphere": 4}[kind])
+    rng = np.random.default_rng({"tiny": 1, "inf": 2, "far": 3, "sphere": 4, "poison": 5, "skew": 6}[kind])
     est = np.zeros((13, count))
     est[0:3] = np.where(np.isfinite(near), near, 0.0)
     est[6] = 1.0
     cov = np.zeros((9, 9, count))
     corr = np.zeros((3, count))
-    if kind == "tiny":                                              # S = P[0:3][0:3] + 0.0625 I with a determinant of 1e-15
+    if kind == "poison":                                            # a full finite covariance with ONE entry that is not finite
+        A = rng.normal(size=(9, 9, count)) * 0.3
+        cov = np.einsum("ikn,jkn->ijn", A, A)
+        for i in range(9):
+            cov[i, i] += 0.5
+        for v in range(count):
+            i, j = POISON_PLACES[(v // len(POISON_VALUES)) % len(POISON_PLACES)]
+            cov[i, j, v] = POISON_VALUES[v % len(POISON_VALUES)]
+    elif kind == "tiny":                                             # S = P[0:3][0:3] + 0.0625 I with a determinant of 1e-15
         for i in range(3):
             cov[i, i] = -0.0625 + 1e-5
             cov[3 + i, 3 + i] = 1.0
@@ -382,6 +446,9 @@ def payload(kind, count, near):
         est[6:10] = q / np.sqrt((q * q).sum(0)) * 1.001             # and an attitude that is not a unit quaternion
         est[10:13] = rng.normal(0, 0.2, (3, count))
         corr = rng.normal(0, 1e-3, (3, count))
+        if kind == "skew":                                          # ... and a covariance that is not symmetric: 0.5 (C + C') of :256 acts
+            B = rng.normal(size=(9, 9, count)) * 0.05
+            cov = cov + (B - B.transpose(1, 0, 2))
     return est, cov.reshape(81, count), corr
 
 
@@ -401,6 +468,11 @@ def run_script(script, est, inputs, sampler=None):
             est.reset(inputs[k], ev[1], ev[2])
             if sampler is not None:
                 sampler.acc.reset(who=slice(ev[1], ev[1] + ev[2]))
+        elif ev[0] == "reset_ranges":
+            for first, count in ev[1]:
+                est.reset(inputs[k], first, count)
+                if sampler is not None:
+                    sampler.acc.reset(who=slice(first, first + count))
         else:
             e13, c81, k3 = payload(ev[1], ev[3], inputs[k])
             est.set_state(e13, c81, k3, first=ev[2])
@@ -425,7 +497,7 @@ def synthetic_inputs(script, n, seed=0):
         elif ev[0] == "measure":
             pos = pos + rng.normal(0, 0.01, (3, n))
             inputs.append((now, pos.copy()))
-        elif ev[0] == "reset":
+        elif ev[0] in ("reset", "reset_ranges"):
             inputs.append(now)
         else:
             inputs.append(pos[:, ev[2]:ev[2] + ev[3]].copy())

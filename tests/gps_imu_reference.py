@@ -1,13 +1,15 @@
 """Offboard::GPSIMUStateEstimator restated in scalar Python, line by line (test infrastructure; the counterpart of
 tests/offboard_reference.py).  The lines cited are those of the reference's
-Components/Components/Offboard/GPSIMUStateEstimator.cpp unless another file is named.  The reference class needs Eigen and
-is not compiled anywhere in this project: this is a RESTATEMENT, not a pin.  tests/gps_estimator_checker.py is the same in
-vectorised numpy and agri-fly_amd/csrc/afe_gps_estimator.hip the same on the device; all three must give the same bits.
+Components/Components/Offboard/GPSIMUStateEstimator.cpp unless another file is named.  tests/gps_estimator_checker.py is the
+same in vectorised numpy and agri-fly_amd/csrc/afe_gps_estimator.hip the same on the device; all three must give the same
+bits.  The class's own text is compiled where it lies by oracle/_ref/gps_probe (against the recording dense stand-in
+oracle/eigen_dense) and tests/test_gps_reference.py holds this file to what it recorded: bit for bit outside Eigen, the
+branch and the finite / non-finite mask exactly, Eigen's finite results within derived bounds.
 
 Python floats are IEEE doubles and nothing is contracted, so a line of C++ double arithmetic is the same line here.  The
 reference's float quirks are kept (f32 below narrows): acosf, the 1e-6f and -9.81f constants, GetUnitVector's float norm, the
-division by 2.0f.  Eigen's evaluation order cannot be known, so this file FIXES one (predict_covariance, update): see the
-header of afe_gps_estimator.hip.
+division by 2.0f.  Eigen's evaluation order cannot be known, so this file FIXES one for finite numbers (predict_covariance,
+update) and takes the DENSE products' behaviour for non-finite ones (tainted): see the header of afe_gps_estimator.hip.
 
 math(op, x): op 0 sin, 1 cos (double), 2 acosf (x is narrowed to float, the float result widened)."""
 import ctypes as _C
@@ -158,8 +160,20 @@ def off_identity_rows(dt, nv, na):
     return rows
 
 
+def tainted(P):
+    """a covariance with an entry that is not finite.  The reference's products are dense: f * _cov * f.transpose() (:195),
+    H * (_cov * H.transpose()) (:224) and (I - L H) * _cov (:255) multiply by the structural zeros of f, H and I - L H too,
+    and 0 * NaN = 0 * Inf = NaN.  One such entry therefore makes every entry of f P f' non-finite whatever f holds, and
+    every entry of S; see predict_covariance and UpdateWithMeasurement."""
+    return not all(_m.isfinite(P[i][j]) for i in range(9) for j in range(9))
+
+
 def predict_covariance(P, rows):
-    """:195, F P F' with F = I + N"""
+    """:195, F P F' with F = I + N.  A tainted P gives NaN in all 81 places (the dense product's mask; where the dense
+    product would hold an infinity -- entry (i, j) for a lone infinity at (k, l) with F[i][k] and F[j][l] both non-zero --
+    this definition says NaN as well: the next update restarts either way)."""
+    if tainted(P):
+        return [[float("nan")] * 9 for _ in range(9)]
     T = [[P[i][j] for j in range(9)] for i in range(9)]
     for i in range(9):
         for j in range(9):
@@ -285,7 +299,7 @@ class GPSIMUStateEstimator:
             self._restart(meas_pos)
             return False
         S, det, adj = innovation(self.cov, c["sigma_pos"] * c["sigma_pos"])                # :224-227
-        finite = all(_m.isfinite(S[i][j]) for i in range(3) for j in range(3))
+        finite = all(_m.isfinite(S[i][j]) for i in range(3) for j in range(3)) and not tainted(self.cov)   # dense: see tainted
         if abs(det) < 1e-10 or not finite:                      # :228-237
             self.count["singular_tiny" if finite else "singular_nonfinite"] += 1
             self._restart(meas_pos)
